@@ -15,11 +15,16 @@ whole-job Mpixels/s = N * frame pixels * steps / max-over-ranks time.
 torch.distributed.run on 127.0.0.1); under a launcher (RANK / WORLD_SIZE in the environment) it is one of them. The JSON says how
 many ranks the RCCL process group really spanned (`ranks.rccl_ranks`: an all-reduce of 1) and every rank's own ms_per_step.
 
-Extra legs (rank 0, N = 1 only):
-    roofline      algorithmic bytes (32 B/px: 16 read + 16 written) / mean kernel time from HIP events
+A plain run sets up, warms up, times --steps steps and prints the headline; everything else it can measure runs only
+with --full:
+    roofline      (rank 0, every N) algorithmic bytes (32 B/px: 16 read + 16 written) / mean kernel time from HIP events
                   recorded around each launch on the launch stream, against the 8.0 TB/s HBM3E peak.
-    cpu_baseline  the CPU oracle ("port" of the reference's convolveSeparablePlane, 1 thread) on a bounded
-                  sample of the same workload.
+    resize, extras, cpu_baseline, cpu_baseline_config5_all_cores
+                  (rank 0, N = 1) the other BASELINE configurations, and the CPU oracle ("port" of the reference's
+                  convolveSeparablePlane, 1 thread) on a bounded sample of the same workload.
+    scatter_gather_config5
+                  (N > 1) BASELINE configs[4] end to end; --scatter-gather asks for it at any N, with or without --full.
+--dump-outputs DIR writes what the last timed step computed (rank 0's frame) to DIR as float32 .npy files.
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -41,6 +46,7 @@ PREWARM_S = 0.5  # untimed clock-ramp phase before the --warmup steps (see main)
 ROWS = COLS = 4096
 SIGMA = 0.6
 METRIC = "Mpixels/s (and % HBM roofline), 5x5 blur + bilinear resize, 4K RGBA"
+DUMP_PIXELS = 1 << 20  # pixels of the last step's frame that --dump-outputs writes
 
 
 def parse_args():
@@ -52,10 +58,14 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=400)
     ap.add_argument("--ring", type=int, default=4, help="distinct (src, dst) frame pairs to rotate through")
     ap.add_argument("--eager", action="store_true", help="launch every step from Python instead of replaying a HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: roofline, resize, extras, CPU baselines (N = 1), scatter / gather (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed seeded sample of the frame)")
     ap.add_argument("--scatter-gather", action="store_true",
                     help="also time BASELINE configs[4] end to end (RCCL scatter -> blur+resize -> gather), 128 frames per GPU; "
-                         "with one GPU the shard loops back through a one-rank RCCL communicator. With --gpus N > 1 this leg runs by default")
-    ap.add_argument("--no-scatter-gather", action="store_true", help="N > 1: skip the configs[4] scatter / compute / gather leg")
+                         "with one GPU the shard loops back through a one-rank RCCL communicator. With --full and --gpus N > 1 this leg runs by default")
+    ap.add_argument("--no-scatter-gather", action="store_true", help="--full, N > 1: skip the configs[4] scatter / compute / gather leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="take roofline.traffic from profiles/traffic.json instead of two rocprofv3 counter passes")
     ap.add_argument("--no-extras", action="store_true")
@@ -72,6 +82,18 @@ def _pin_to_one_core():
         return before, core
     except (AttributeError, OSError):
         return None, None
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the (ROWS, COLS, 4) f32 frame the last timed step wrote, sampled at DUMP_PIXELS pixels whose flat indices
+    (row * COLS + col, ascending) come from a fixed seed, so every run with the same arguments writes the same positions.
+    The whole frame is 256 MiB, the sample 16 MiB."""
+    import numpy as np
+    import torch
+    idx = np.sort(np.random.default_rng(0).choice(ROWS * COLS, DUMP_PIXELS, replace=False))
+    sample = frame.reshape(ROWS * COLS, 4)[torch.from_numpy(idx).to(frame.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "gaussian_blur_rgba_f32.npy"), np.ascontiguousarray(sample, np.float32))
 
 
 def parity_metrics(got, want):
@@ -143,7 +165,7 @@ def launch_ranks(args) -> int:
 
 def main():
     args = parse_args()
-    if args.gpus > 1 and not args.no_scatter_gather:
+    if args.full and args.gpus > 1 and not args.no_scatter_gather:
         args.scatter_gather = True  # the N-GPU run is the one that can put bytes on xGMI: BASELINE configs[4] is part of it unless switched off
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -254,6 +276,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     region_ms_per_launch = ev_begin.elapsed_time(ev_end) / args.steps
+    if args.dump_outputs and rank == 0:  # before the --full legs, which launch the blur into the same ring again
+        dump_outputs(args.dump_outputs, dsts[(args.steps - 1) % ring])
     from zignal_amd import sharding
     ctl = torch.device("cpu") if shared_gpu else torch.device("cuda", local_rank)  # where the control-plane collectives run
     own_ms = elapsed / args.steps * 1e3
@@ -280,7 +304,7 @@ def main():
                    "parallelism": f"frame-sharded x{world}, no data-path collective"},
     }
 
-    if rank == 0:
+    if args.full and rank == 0:
         # Kernel time per launch = HIP events around the timed region (above) / launches in it: device time on the launch stream,
         # inter-launch gaps included, so it can only overstate the kernel. Cross-check: event pairs around 200 single eager
         # launches (each pair also brackets its launch overhead), and the rocprofv3 mean under profiles/.
@@ -313,7 +337,7 @@ def main():
                               "kernel_ms_eager_event_pairs_mean": round(eager_mean_ms, 5),
                               "kernel_ms_eager_event_pairs_median": round(kernel_ms[len(kernel_ms) // 2], 5),
                               "algorithmic_bytes_per_launch": alg_bytes}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # The metric names two ops: the bilinear resize of BASELINE configs[2] stands beside the blur, same arithmetic.
         try:
             result["resize"] = resize_headline(zg, torch, not args.no_live_traffic)

@@ -24,7 +24,7 @@ def test_bench_two_rank_path_on_one_gpu():
     pytest.importorskip("torch")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ZG_BENCH_SHARED_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "100"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "100", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -39,6 +39,39 @@ def test_bench_two_rank_path_on_one_gpu():
     sg = res["scatter_gather_config5"]
     assert sg["frames"] == 256 and sg["kernel_only"]["Mpixels/s"] > 0 and sg["host_staged_pcie"]["Mpixels/s"] > 0
     assert "skipped" in sg["end_to_end_xgmi"]  # every rank shares cuda:0 under the test hook: RCCL needs one GPU per rank
+
+
+@pytest.mark.parametrize("steps", [40, 41])  # 40: graph replay; 41 is no multiple of the ring of 4, so every step is an eager launch
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step(oracle, tmp_path, steps):
+    """A plain run carries the headline and none of the --full legs; --dump-outputs writes the frame of the last timed step (ring slot
+    (steps - 1) % 4, source torch.rand seeded 2 on cuda:0) at its seeded sample of pixels, bit-identical to the oracle's blur of that source."""
+    import json
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "8", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == steps and res["ms_per_step"] > 0 and res["value"] > 0
+    assert res["unit"] == "Mpixels/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["config"]["launch"] == ("eager" if steps % 4 else "hipGraph replay, 40 launches per graph")
+    for leg in ("roofline", "resize", "extras", "cpu_baseline", "cpu_baseline_config5_all_cores", "scatter_gather_config5"):
+        assert leg not in res, leg
+    assert [f.name for f in tmp_path.iterdir()] == ["gaussian_blur_rgba_f32.npy"]
+    got = np.load(tmp_path / "gaussian_blur_rgba_f32.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 20, 4) and got.nbytes <= 64 << 20
+
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(2)
+    srcs = [torch.rand((4096, 4096, 4), dtype=torch.float32, device="cuda", generator=gen) for _ in range(4)]
+    src = srcs[(steps - 1) % 4].cpu().numpy()
+    del srcs
+    idx = np.sort(np.random.default_rng(0).choice(4096 * 4096, 1 << 20, replace=False))
+    want = oracle.gaussian_blur(src, 0.6).reshape(-1, 4)[idx]
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 def test_bench_counts_its_rccl_ranks_and_times_the_three_distribution_routes():

@@ -3,7 +3,7 @@
 # zignal_amd/variants/libzignal_hip_<variant>.so, side by side (ms per call).
 v=$1; re=$2
 for lib in "" "$PWD/zignal_amd/variants/libzignal_hip_$v.so"; do
-  ZIGNAL_HIP_LIBRARY=$lib ZG_BENCH_EXTRAS="$re" python bench.py --steps 200 --warmup 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | python -c "
+  ZIGNAL_HIP_LIBRARY=$lib ZG_BENCH_EXTRAS="$re" python bench.py --full --steps 200 --warmup 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('LIB', '${lib:-product}', 'headline ms', d['ms_per_step'], 'resize', d.get('resize',{}).get('ms_per_step'))
