@@ -395,6 +395,33 @@ ZG_API int zg_morph_host(const zg_image *src, const zg_image *dst, const uint8_t
 ZG_API int zg_canny(const zg_image *src, const zg_image *dst, float sigma, float low_threshold, float high_threshold, zg_stream stream);
 ZG_API int zg_canny_host(const zg_image *src, const zg_image *dst, float sigma, float low_threshold, float high_threshold);
 
+/* ---- features: FAST (src/features/Fast.zig, KeyPoint.zig) ------------------------------------------------------------ */
+
+/* KeyPoint (src/features/KeyPoint.zig:9-28), 28 B, field for field. */
+typedef struct zg_keypoint {
+    float x, y, size, angle, response;
+    int32_t octave, class_id;
+} zg_keypoint;
+/* Fast.detect (src/features/Fast.zig:38-72) with Fast{threshold, nonmax_suppression, min_contiguous} (:16-24): the keypoints of an
+ * Image(u8) (a view is fine) in the reference's order — raster order without NMS; with NMS (:155-254) the 20 x 20 cells of the grid
+ * anchored at the corners' smallest row and column, row-major, each by descending response with ties in raster order. x = col,
+ * y = row relative to the view, size 7, angle -1, response = the integer score, octave 0, class_id -1. keypoints / count: device
+ * pointers. *count receives the number of keypoints the reference returns, which may exceed capacity; the first
+ * min(*count, capacity) of its list are written. threshold or min_contiguous > 255 (the reference's u8) and rows <= 7 or cols <= 7
+ * (the reference's assert, :39) are ZG_ERR_INVALID_ARGUMENT; a pixel type other than u8 is ZG_ERR_UNSUPPORTED. Asynchronous on
+ * `stream`, no host synchronisation, capturable into a graph. */
+ZG_API int zg_fast_detect(const zg_image *src, uint32_t threshold, uint32_t min_contiguous, int nonmax_suppression,
+                          zg_keypoint *keypoints, uint32_t capacity, uint32_t *count, zg_stream stream);
+/* Host pointers, synchronous. keypoints may be NULL with capacity 0 to query the count (the zg_gaussian_kernel convention). */
+ZG_API int zg_fast_detect_host(const zg_image *src, uint32_t threshold, uint32_t min_contiguous, int nonmax_suppression,
+                               zg_keypoint *keypoints, uint32_t capacity, uint32_t *count);
+/* n independent Fast.detect calls in one pass per stage, e.g. the levels of a pyramid with ORB's per-level threshold
+ * (src/features/orb.zig:165-176, 511-517). Image i writes keypoints[offsets[i] .. offsets[i] + capacities[i]) and counts[i].
+ * thresholds, capacities, offsets: host arrays; keypoints, counts: device. Equal to n calls of zg_fast_detect, bit for bit. */
+ZG_API int zg_fast_detect_batch(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t min_contiguous,
+                                int nonmax_suppression, zg_keypoint *keypoints, const uint32_t *capacities,
+                                const uint64_t *offsets, uint32_t *counts, zg_stream stream);
+
 /* Diagnostics, not part of Image(T): shenCastan's smoothing stage on its own — isefFilter2D (src/image/edges.zig:308-349, a private
  * function there): isefFilter1D (:283-305) along every row, then along every column, of a contiguous plane on the device: Image(f32), or
  * Image(u8) taken as as(f32, u8) (what shenCastan feeds it, and how the detector's byte plane reaches the row pass). src -> dst (Image(f32);

@@ -235,6 +235,10 @@ pub const c = struct {
     pub extern fn zg_rotate_into(src: *const ZgImage, dst: *const ZgImage, angle: f32, cos_a: f32, sin_a: f32, method: *const ZgMethod, border: c_int, stream: ?*anyopaque) c_int;
     pub extern fn zg_sharpen(src: *const ZgImage, dst: *const ZgImage, radius: u32, stream: ?*anyopaque) c_int;
     pub extern fn zg_isef_smooth(src: *const ZgImage, dst: *const ZgImage, smooth: f32, stream: ?*anyopaque) c_int;
+    pub const ZgKeypoint = extern struct { x: f32, y: f32, size: f32, angle: f32, response: f32, octave: i32, class_id: i32 }; // KeyPoint.zig:9-28
+    pub extern fn zg_fast_detect(src: *const ZgImage, threshold: u32, min_contiguous: u32, nonmax_suppression: c_int, keypoints: ?[*]ZgKeypoint, capacity: u32, count: *u32, stream: ?*anyopaque) c_int;
+    pub extern fn zg_fast_detect_host(src: *const ZgImage, threshold: u32, min_contiguous: u32, nonmax_suppression: c_int, keypoints: ?[*]ZgKeypoint, capacity: u32, count: *u32) c_int;
+    pub extern fn zg_fast_detect_batch(images: [*]const ZgImage, n: u32, thresholds: [*]const u32, min_contiguous: u32, nonmax_suppression: c_int, keypoints: ?[*]ZgKeypoint, capacities: [*]const u32, offsets: [*]const u64, counts: [*]u32, stream: ?*anyopaque) c_int;
     pub extern fn zg_shen_castan(src: *const ZgImage, dst: *const ZgImage, smooth: f32, window_size: u32, high_ratio: f32, low_rel: f32, hysteresis: c_int, use_nms: c_int, stream: ?*anyopaque) c_int;
     pub extern fn zg_sobel(src: *const ZgImage, dst: *const ZgImage, stream: ?*anyopaque) c_int;
     pub extern fn zg_threshold_adaptive_mean(src: *const ZgImage, dst: *const ZgImage, radius: u32, c: f32, stream: ?*anyopaque) c_int;
@@ -1096,5 +1100,62 @@ pub const jpeg = struct {
         try checkJpeg(c.zg_jpeg_encode_host(&Image(T).desc(image.base), space, options, &mem, &len));
         defer c.zg_jpeg_free(mem);
         return allocator.dupe(u8, mem.?[0..len]);
+    }
+};
+
+// ---- features: FAST (reference src/features/Fast.zig, KeyPoint.zig) --------------------------------------------------
+
+/// KeyPoint (src/features/KeyPoint.zig:9-28) laid out as zg_keypoint: the library writes these bytes directly.
+pub const KeyPoint = c.ZgKeypoint;
+comptime {
+    std.debug.assert(@sizeOf(KeyPoint) == 28);
+}
+
+/// Fast (src/features/Fast.zig:16-24): same fields, same defaults, same list as the reference's detect (:38-72), order included.
+pub const Fast = struct {
+    threshold: u8 = 20,
+    nonmax_suppression: bool = true,
+    min_contiguous: u8 = 9,
+
+    /// reference src/features/Fast.zig:38-72: the host image crosses to the device and back; the count is asked first.
+    pub fn detect(self: Fast, allocator: std.mem.Allocator, image: zignal.Image(u8)) ![]KeyPoint {
+        const d = Image(u8).desc(image);
+        var n: u32 = 0;
+        try check(c.zg_fast_detect_host(&d, self.threshold, self.min_contiguous, @intFromBool(self.nonmax_suppression), null, 0, &n));
+        const out = try allocator.alloc(KeyPoint, n);
+        errdefer allocator.free(out);
+        var m: u32 = 0;
+        if (n > 0) try check(c.zg_fast_detect_host(&d, self.threshold, self.min_contiguous, @intFromBool(self.nonmax_suppression), out.ptr, n, &m));
+        return out;
+    }
+
+    /// The device form: zg_fast_detect on the image's stream into `keypoints` / `count` (device memory from zg_malloc; at most
+    /// `capacity` keypoints are written, *count receives the full length). Asynchronous, capturable into a graph.
+    pub fn detectInto(self: Fast, image: DeviceImage(u8), keypoints: ?[*]KeyPoint, capacity: u32, count: *u32) !void {
+        try check(c.zg_fast_detect(&image.desc(), self.threshold, self.min_contiguous, @intFromBool(self.nonmax_suppression), keypoints, capacity, count, image.stream));
+    }
+
+    /// detect on a device image, returned in host memory: device scratch for `capacity` keypoints, once more with the exact length
+    /// when the list is longer (the result is deterministic).
+    pub fn detectDevice(self: Fast, allocator: std.mem.Allocator, image: DeviceImage(u8)) ![]KeyPoint {
+        var capacity: u32 = 1 << 16;
+        while (true) {
+            var mem: ?*anyopaque = null;
+            try check(c.zg_malloc(&mem, @as(usize, capacity) * @sizeOf(KeyPoint) + 4));
+            defer _ = c.zg_free(mem);
+            const kps: [*]KeyPoint = @ptrCast(@alignCast(mem.?));
+            const dcount: *u32 = @ptrCast(@alignCast(@as([*]u8, @ptrCast(mem.?)) + @as(usize, capacity) * @sizeOf(KeyPoint)));
+            try self.detectInto(image, kps, capacity, dcount);
+            var n: u32 = 0;
+            try check(c.zg_memcpy_d2h(&n, dcount, 4, image.stream));
+            if (n > capacity) {
+                capacity = n;
+                continue;
+            }
+            const out = try allocator.alloc(KeyPoint, n);
+            errdefer allocator.free(out);
+            if (n > 0) try check(c.zg_memcpy_d2h(out.ptr, kps, @as(usize, n) * @sizeOf(KeyPoint), image.stream));
+            return out;
+        }
     }
 };

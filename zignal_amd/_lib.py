@@ -81,6 +81,12 @@ class ZgJpegEncodeOptions(C.Structure):
     _fields_ = [("quality", C.c_int), ("subsampling", C.c_int), ("density_dpi", C.c_int), ("comment", C.c_char_p), ("comment_len", C.c_size_t)]
 
 
+class ZgKeypoint(C.Structure):
+    """zg_keypoint == KeyPoint (src/features/KeyPoint.zig:9-28)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("size", C.c_float), ("angle", C.c_float), ("response", C.c_float),
+                ("octave", C.c_int32), ("class_id", C.c_int32)]
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -223,6 +229,9 @@ _SIGNATURES = {
     "zg_canny": [_IMG, _IMG, C.c_float, C.c_float, C.c_float, C.c_void_p],
     "zg_canny_host": [_IMG, _IMG, C.c_float, C.c_float, C.c_float],
     "zg_isef_smooth": [_IMG, _IMG, C.c_float, C.c_void_p],
+    "zg_fast_detect": [_IMG, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_fast_detect_host": [_IMG, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, _U32P],
+    "zg_fast_detect_batch": [_IMG, C.c_uint32, _U32P, C.c_uint32, C.c_int, C.c_void_p, _U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
     "zg_shen_castan": [_IMG, _IMG, C.c_float, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p],
     "zg_shen_castan_host": [_IMG, _IMG, C.c_float, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int],
     "zg_motion_blur_linear": [_IMG, _IMG, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p],

@@ -535,4 +535,53 @@ struct Pipeline {
     }
 };
 
+// ---- features: FAST (src/features/Fast.zig, KeyPoint.zig) ----
+using KeyPoint = zg_keypoint; // KeyPoint.zig:9-28, field for field
+static_assert(sizeof(KeyPoint) == 28, "zg_keypoint is KeyPoint's 28 bytes");
+
+// Fast (src/features/Fast.zig:16-24): the reference's fields and defaults; detect returns its list (:38-72), order included, bit for bit.
+struct Fast {
+    uint8_t threshold = 20;
+    bool nonmax_suppression = true;
+    uint8_t min_contiguous = 9;
+
+    // host image: the count first, then the list (two synchronous calls)
+    std::vector<KeyPoint> detect(const Image<uint8_t> &image) const {
+        const zg_image s = image.desc();
+        uint32_t n = 0;
+        check(zg_fast_detect_host(&s, threshold, min_contiguous, nonmax_suppression, nullptr, 0, &n));
+        std::vector<KeyPoint> out(n);
+        if (n) check(zg_fast_detect_host(&s, threshold, min_contiguous, nonmax_suppression, out.data(), n, &n));
+        return out;
+    }
+    // device image, list back on the host: device scratch for `capacity` keypoints, run once more with the exact length when the list is
+    // longer (the result is deterministic). Synchronises the image's stream.
+    std::vector<KeyPoint> detect(const DeviceImage<uint8_t> &image, uint32_t capacity = 1u << 16) const {
+        for (;;) {
+            void *mem = nullptr;
+            check(zg_malloc(&mem, (size_t)capacity * sizeof(KeyPoint) + sizeof(uint32_t)));
+            KeyPoint *kps = (KeyPoint *)mem;
+            uint32_t *dcount = (uint32_t *)(kps + capacity);
+            uint32_t n = 0;
+            const zg_image s = image.desc();
+            int rc = zg_fast_detect(&s, threshold, min_contiguous, nonmax_suppression, kps, capacity, dcount, image.stream());
+            if (rc == ZG_OK) rc = zg_memcpy_d2h(&n, dcount, sizeof(n), image.stream());
+            std::vector<KeyPoint> out;
+            if (rc == ZG_OK && n <= capacity) {
+                out.resize(n);
+                if (n) rc = zg_memcpy_d2h(out.data(), kps, (size_t)n * sizeof(KeyPoint), image.stream());
+            }
+            (void)zg_free(mem);
+            check(rc);
+            if (n <= capacity) return out;
+            capacity = n;
+        }
+    }
+    // asynchronous device form (zg_fast_detect): keypoints / count are device memory; *count receives the full length
+    void detectInto(const DeviceImage<uint8_t> &image, KeyPoint *keypoints, uint32_t capacity, uint32_t *count) const {
+        const zg_image s = image.desc();
+        check(zg_fast_detect(&s, threshold, min_contiguous, nonmax_suppression, keypoints, capacity, count, image.stream()));
+    }
+};
+
 } // namespace zignal

@@ -776,6 +776,104 @@ class ImagePyramid:
         return sum(l.rows * l.cols for l in self.levels)
 
 
+# KeyPoint (reference src/features/KeyPoint.zig:9-28) as a numpy structured dtype: the bytes of zg_keypoint.
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
+                           ("octave", "<i4"), ("class_id", "<i4")])
+assert KEYPOINT_DTYPE.itemsize == C.sizeof(L.ZgKeypoint)
+
+
+class Fast:
+    """Fast (reference src/features/Fast.zig): the FAST corner detector with the reference's fields and defaults (:16-24).
+    `detect` returns the reference's keypoint list, order included, as a KEYPOINT_DTYPE array, bit for bit."""
+
+    DEFAULT_CAPACITY = 1 << 16
+
+    def __init__(self, threshold: int = 20, nonmax_suppression: bool = True, min_contiguous: int = 9):
+        self.threshold, self.nonmax_suppression, self.min_contiguous = int(threshold), bool(nonmax_suppression), int(min_contiguous)
+
+    def __repr__(self):
+        return f"Fast(threshold={self.threshold}, nonmax_suppression={self.nonmax_suppression}, min_contiguous={self.min_contiguous})"
+
+    @staticmethod
+    def _image(image) -> "Image":
+        return image if isinstance(image, Image) else Image(image)
+
+    def detect(self, image, capacity: Optional[int] = None) -> np.ndarray:
+        """Fast.detect (:38-72). Host images go through zg_fast_detect_host, device images through zg_fast_detect on the current
+        stream (this call synchronises it to read the count). When the list is longer than `capacity` the call runs once more
+        with the exact length; the result is deterministic, so the second run returns the same list."""
+        img = self._image(image)
+        cap = self.DEFAULT_CAPACITY if capacity is None else int(capacity)
+        if not img.on_device:
+            return self._detect_host(img, cap)
+        kps = torch.empty(max(cap, 1) * KEYPOINT_DTYPE.itemsize, dtype=torch.uint8, device=img.data.device)
+        count = torch.zeros(1, dtype=torch.int32, device=img.data.device)
+        self.detect_into(img, kps, count, cap)
+        n = int(count.item())
+        if n > cap:
+            return self.detect(img, n)
+        return kps[: n * KEYPOINT_DTYPE.itemsize].cpu().numpy().view(KEYPOINT_DTYPE).copy()
+
+    def _detect_host(self, img: "Image", cap: int) -> np.ndarray:
+        out = np.empty(cap, KEYPOINT_DTYPE)
+        count = C.c_uint32()
+        s = img._desc()
+        L.check(L.lib().zg_fast_detect_host(C.byref(s), self.threshold, self.min_contiguous, int(self.nonmax_suppression),
+                                            out.ctypes.data if cap else None, cap, C.byref(count)))
+        if count.value > cap:
+            return self._detect_host(img, count.value)
+        return out[: count.value].copy()
+
+    def detect_into(self, image, keypoints, count, capacity: Optional[int] = None) -> None:
+        """Asynchronous device form: zg_fast_detect on the current stream into `keypoints` (a device tensor of at least
+        capacity x 28 bytes; capacity defaults to what it holds) and `count` (a device tensor of at least 4 bytes, receives
+        the full length as a u32). Nothing is synchronised."""
+        img = self._image(image)
+        if not img.on_device or not _is_torch(keypoints) or not _is_torch(count):
+            raise ValueError("detect_into takes a device image and device tensors")
+        nbytes = keypoints.numel() * keypoints.element_size()
+        cap = nbytes // KEYPOINT_DTYPE.itemsize if capacity is None else int(capacity)
+        if cap * KEYPOINT_DTYPE.itemsize > nbytes or count.numel() * count.element_size() < 4:
+            raise ValueError("keypoints or count tensor too small")
+        s = img._desc()
+        with torch.cuda.device(img.data.device):
+            L.check(L.lib().zg_fast_detect(C.byref(s), self.threshold, self.min_contiguous, int(self.nonmax_suppression),
+                                           C.c_void_p(keypoints.data_ptr()), cap, C.c_void_p(count.data_ptr()), img._stream()))
+
+    def detect_batch(self, images, thresholds=None, capacity: Optional[int] = None) -> List[np.ndarray]:
+        """n Fast.detect calls, one per image (e.g. ImagePyramid.levels), with thresholds[i] instead of self.threshold where
+        given (ORB's per-level thresholds, orb.zig:165-176). Device images go through zg_fast_detect_batch (one pass per stage
+        for all of them); host images through zg_fast_detect_host, one by one."""
+        imgs = [self._image(i) for i in images]
+        ts = [self.threshold] * len(imgs) if thresholds is None else [int(t) for t in thresholds]
+        if len(ts) != len(imgs):
+            raise ValueError("one threshold per image")
+        if not imgs:
+            return []
+        if not all(i.on_device for i in imgs):
+            if any(i.on_device for i in imgs):
+                raise ValueError("images must all be host or all be device images")
+            return [Fast(t, self.nonmax_suppression, self.min_contiguous).detect(i, capacity) for i, t in zip(imgs, ts)]
+        caps = [self.DEFAULT_CAPACITY if capacity is None else int(capacity)] * len(imgs)
+        while True:
+            offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.uint64)
+            dev = imgs[0].data.device
+            kps = torch.empty(max(int(offs[-1]), 1) * KEYPOINT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            counts = torch.zeros(len(imgs), dtype=torch.int32, device=dev)
+            descs = (L.ZgImage * len(imgs))(*[i._desc() for i in imgs])
+            th = (C.c_uint32 * len(imgs))(*ts)
+            cp = (C.c_uint32 * len(imgs))(*caps)
+            of = (C.c_uint64 * len(imgs))(*[int(o) for o in offs[:-1]])
+            with torch.cuda.device(dev):
+                L.check(L.lib().zg_fast_detect_batch(descs, len(imgs), th, self.min_contiguous, int(self.nonmax_suppression),
+                                                     C.c_void_p(kps.data_ptr()), cp, of, C.c_void_p(counts.data_ptr()), imgs[0]._stream()))
+            n = counts.cpu().numpy().astype(np.int64)
+            if all(int(c) <= cap for c, cap in zip(n, caps)):
+                host = kps.cpu().numpy().view(KEYPOINT_DTYPE)
+                return [host[int(o): int(o) + int(c)].copy() for o, c in zip(offs[:-1], n)]
+            caps = [max(int(c), cap) for c, cap in zip(n, caps)]
+
+
 class ProjectiveTransform:
     """reference src/geometry/transforms.zig:197-231 (f32 matrix, project = M [x y 1]^T scaled by 1/w)."""
     kind = L.TRANSFORM_PROJECTIVE
