@@ -121,6 +121,7 @@ ALTERNATIVE_FORMS = {
     "ZIGNAL_HIP_NO_TILE_F32": "the LDS-tiled k_sep_f32x4 instead of the tile-per-wave k_sep_tile_f32 for Image(f32) planes",
     "ZIGNAL_HIP_RESIZE_FORM=0": "round 4's four-row workgroups in XCD-major order for every bilinear Rgba(u8) resize (reductions use one-wave workgroups in address order)",
     "ZIGNAL_HIP_NO_PYRAMID_FUSE": "gaussianBlur into a blurred plane then resize for every level of an Image(u8) pyramid instead of the column pass fused with the bilinear taps",
+    "ZIGNAL_HIP_NO_PYRAMID_TILE": "round 5's routes (multi-job kernels, fused column pass) for every Image(u8) pyramid level instead of the tile kernel k_pyr_tile",
     "ZIGNAL_HIP_NO_PYRAMID_BATCH": "every long-tap level of an Image(u8) pyramid with its own row- and column-pass launches instead of the multi-job kernels (k_rows_u8f_multi, k_cols_u8f_multi, k_cols_bilinear_u8_multi)",
     "ZIGNAL_HIP_RESIZE_U8_ROWS=0": "k_resize_bilinear_u8 (one output row per wave, taps per pixel) for every Image(u8) bilinear resize instead of k_resize_bilinear_u8_rows<2> below a ratio of 2",
     "ZIGNAL_HIP_RESIZE_U8_ROWS=4": "k_resize_bilinear_u8_rows<4>: four output rows per wave",

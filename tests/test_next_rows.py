@@ -140,8 +140,9 @@ def test_pyramid_parity(oracle, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", ((33, 256), (31, 272), (32, 256), (64, 1040), (95, 1024), (500, 2064), (1080, 1920), (20, 640)))
 def test_pyramid_u8_fused_levels(oracle, shape):
-    """Image(u8) levels come from k_rows_u8f + k_cols_bilinear_u8 (the column pass evaluated at the resize's taps, 31-row bands): band seams, the
-    anchored last band, planes shorter than a band, mirrored right / bottom taps, scale 1 (a blurred copy) and both band-loop forms (inside / edge)."""
+    """Image(u8) levels come from k_pyr_tile (reductions from 1.3 on whose taps fit, pyramid_tile.hip) and the others from the multi-job kernels
+    (k_rows_u8f_multi, then k_cols_bilinear_u8_multi: the column pass evaluated at the resize's taps, 31-row bands): band seams, the anchored last
+    band, planes shorter than a band, mirrored right / bottom taps, scale 1 (a blurred copy) and both band-loop forms (inside / edge)."""
     src = oracle.synth_u8(90 + shape[0], shape)
     for n, sf, sigma in ((4, 1.2, 1.6), (6, 1.5, 1.0), (3, 1.05, 0.8), (3, 2.0, 3.0), (3, 2.1, 2.91), (9, 1.2, 1.6)):
         want = oracle.pyramid(src, n, sf, sigma)

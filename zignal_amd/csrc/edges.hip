@@ -629,6 +629,8 @@ static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, flo
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
     const uint32_t rows = src->rows, cols = src->cols;
     const size_t n = (size_t)rows * cols;
+    // run_hysteresis's limit, checked before any scratch or launch: the frame's stages would otherwise run (and allocate 16 bytes a pixel) to be refused at the end
+    ZG_REQUIRE(n <= 0x7fffffffu, ZG_ERR_UNSUPPORTED, "canny: hysteresis labels are 32-bit (rows * cols must stay below 2^31)");
 
     // scratch: grey f32 | blurred f32 | state u8 | hysteresis work
     char *scratch = nullptr;
@@ -1234,6 +1236,7 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
     const uint32_t rows = src->rows, cols = src->cols;
     const size_t n = (size_t)rows * cols, nf = (n + 3) / 4 * 4;
+    ZG_REQUIRE(!hysteresis || n <= 0x7fffffffu, ZG_ERR_UNSUPPORTED, "shenCastan: hysteresis labels are 32-bit (rows * cols must stay below 2^31)"); // as in canny_impl
 
     // scratch: f32 planes grey | smoothed | temp (ISEF) then grey*BLI | gradient | three SATs; u8 planes BLI | candidates | NMS | state;
     // histogram (256) | thresholds (2) | hysteresis work
