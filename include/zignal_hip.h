@@ -161,9 +161,28 @@ ZG_API int zg_event_synchronize(zg_event e);
 ZG_API int zg_event_elapsed_ms(zg_event start, zg_event stop, float *ms); /* device time between two recorded events */
 /* Everything the library enqueues on `stream` (not the default stream) between begin and end becomes one launchable
  * graph; host-side work of the captured calls (taps, tables, checks) is done at capture time. Scratch that captured calls
- * take belongs to the graph and is freed by zg_graph_destroy. Captures ended by somebody else (torch.cuda.graph around Image
- * calls, a caller's own hipStreamEndCapture) cannot be followed: their scratch stays reserved until zg_release_graph_scratch(),
- * to be called once those graphs are destroyed (it skips captures still in progress). */
+ * take, and the cached device tables their kernels read (the Lanczos axis tables of Rgb(u8) / Rgba(u8) resizes), belong to
+ * the graph and are released by zg_graph_destroy; a replay never reads memory the library has freed. Captures ended by
+ * somebody else (torch.cuda.graph around Image calls, a caller's own hipStreamEndCapture) cannot be followed: their scratch
+ * and tables stay reserved until zg_release_graph_scratch(), to be called once those graphs are destroyed (it skips captures
+ * still in progress). When zg_graph_end_capture fails, what the capture took is released at once.
+ * Calls that cannot be recorded return ZG_ERR_UNSUPPORTED while their stream is capturing (zg_last_error() names the
+ * capture). They refuse before they enqueue anything, so the capture stays valid. Every other call of this header that
+ * takes a stream is capturable, except the stream / event synchronisation of the runtime section. The refused calls:
+ *   zg_convolve with a kernel larger than 15 x 15 taps (either side) on the wide-kernel route;
+ *   zg_conv_separable(_planes) / zg_gaussian_blur(_planes) with more than 255 taps where the two-pass route takes them;
+ *   any call with a caller's zg_method.lanczos_lut or srgb_lut (zg_resize_convert and zg_batch_pipeline check every table
+ *   up front); zg_resize_lanczos_weights;
+ *   zg_threshold_otsu with a non-NULL threshold_out (NULL is capturable);
+ *   zg_png_decode, zg_png_encode, zg_jpeg_decode, zg_jpeg_encode;
+ *   the synchronous copies zg_memcpy_h2d, zg_memcpy_d2h, zg_image_upload, zg_image_download (the _async copies are
+ *   capturable);
+ *   first use of a library table: the first call of a process on a device that samples through the 1025-entry Lanczos table
+ *   (Lanczos warp / rotate / extract / insert / letterbox, and resize of pixel types other than Rgb(u8) / Rgba(u8)), the first
+ *   conversion of u8 pixels that needs the sRGB table (to Xyz, Oklab or a float-only space), and a Lanczos resize of Rgb(u8)
+ *   / Rgba(u8) to a geometry that is not among the last 64 resized. Make one such call outside the capture first. In a
+ *   multi-step call (zg_resize_convert, zg_batch_pipeline, zg_pyramid_build) a first-use refusal can come after earlier steps
+ *   were recorded: discard that capture. */
 ZG_API int zg_graph_begin_capture(zg_stream stream);
 ZG_API int zg_graph_end_capture(zg_stream stream, zg_graph *out);
 ZG_API int zg_graph_launch(zg_graph graph, zg_stream stream);
@@ -376,7 +395,7 @@ ZG_API int zg_equalize_host(const zg_image *img);
 /* Image(u8) binarisation and binary morphology (src/image.zig:845-914 -> src/image/binary.zig). Image(u8) only
  * (ZG_ERR_UNSUPPORTED otherwise, a compile error in the reference).
  * thresholdOtsu (:38-84): out = src > t ? 255 : 0; *threshold_out (host pointer, may be NULL) receives t, which
- * synchronises `stream`. thresholdAdaptiveMean (:86-118): out = src > windowMean(radius) - c; radius 0 is
+ * synchronises `stream` (so it is refused under capture: pass NULL there). thresholdAdaptiveMean (:86-118): out = src > windowMean(radius) - c; radius 0 is
  * error.InvalidRadius -> ZG_ERR_INVALID_ARGUMENT. zg_morph (:121-281): op 0 dilate, 1 erode, 2 open, 3 close; kernel is a
  * host array of kernel_rows x kernel_cols bytes (non-zero = on; odd sizes, else error.InvalidKernelSize); src may alias dst. */
 ZG_API int zg_threshold_otsu(const zg_image *src, const zg_image *dst, uint8_t *threshold_out, zg_stream stream);

@@ -227,6 +227,9 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
     ZG_REQUIRE(pixel_valid(pixel), ZG_ERR_INVALID_ARGUMENT, "pipeline: invalid pixel type %d", pixel);
     ZG_REQUIRE(n_steps == 0 || steps != nullptr, ZG_ERR_INVALID_ARGUMENT, "pipeline: null steps");
     hipStream_t s = as_stream(stream);
+    for (uint32_t i = 0; i < n_steps; ++i) // a step with a caller's table would upload it after earlier steps were enqueued: refused up front
+        if ((steps[i].srgb_lut || steps[i].method.lanczos_lut) && refuse_under_capture(s, "zg_batch_pipeline with a caller's sRGB or Lanczos table in a step"))
+            return ZG_ERR_UNSUPPORTED;
     // shapes after every step (validates all steps before anything is enqueued, like the CLI validates its recipe first: pipeline.zig:108-114)
     std::vector<Frames> shape(n_steps + 1);
     shape[0] = Frames{nullptr, 0, rows, cols, pixel, space};

@@ -112,13 +112,14 @@ static int check_u8_pair(const zg_image *src, const zg_image *dst, const char *w
 static int otsu_impl(const zg_image *src, const zg_image *dst, uint8_t *threshold_host, hipStream_t s) {
     int rc;
     if ((rc = check_u8_pair(src, dst, "thresholdOtsu"))) return rc;
+    if (threshold_host && (rc = refuse_under_capture(s, "zg_threshold_otsu with a threshold_out (it reads the threshold back to the host)"))) return rc;
     if (threshold_host) *threshold_host = 0;
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
     char *scratch = nullptr;
     if ((rc = scratch_alloc((void **)&scratch, 256 * sizeof(unsigned int) + 16, s))) return rc;
     unsigned int *hist = (unsigned int *)scratch;
     uint8_t *thr = (uint8_t *)(hist + 256);
-    if (hipMemsetAsync(hist, 0, 256 * sizeof(unsigned int), s) != hipSuccess) { scratch_free(scratch, s); ZG_HIP(hipErrorUnknown); }
+    if ((rc = fill_async(hist, 0, 256 * sizeof(unsigned int), s))) { scratch_free(scratch, s); return rc; }
     hipLaunchKernelGGL(k_hist_u8, dim3(ceil_div(src->cols, 64), ceil_div(src->rows, 64)), dim3(256), 0, s, dimg(src), hist);
     hipLaunchKernelGGL(k_otsu_threshold, dim3(1), dim3(64), 0, s, (const unsigned int *)hist, thr, (double)((size_t)src->rows * src->cols));
     hipLaunchKernelGGL(k_apply_threshold, dim3(ceil_div(src->cols, 256), src->rows), dim3(256), 0, s, dimg(src), dimg(dst), (const uint8_t *)thr);

@@ -253,6 +253,7 @@ static int convolve_impl(const zg_image *src, const zg_image *dst, const float *
         });
     }
     void *taps = nullptr; // larger: taps from device memory (uploaded synchronously: not capturable)
+    if ((rc = refuse_under_capture(s, "zg_convolve with more than 15 x 15 taps (the taps are uploaded from host memory)"))) return rc;
     if ((rc = scratch_alloc(&taps, nk * 4, s))) return rc;
     rc = upload_pageable(taps, is_float ? (const void *)kernel : (const void *)ik.data(), nk * 4, s);
     if (rc == ZG_OK)

@@ -493,6 +493,8 @@ static int launch_two_pass(const zg_image *src, const zg_image *dst, const SepPl
     using Temp = typename Arith<MODE>::Temp;
     constexpr int C = Px<PIX>::C;
     const size_t temp_bytes = (size_t)src->rows * src->cols * temp_lanes<C>() * sizeof(Temp);
+    if (p.nkx > MAX_TAPS || p.nky > MAX_TAPS)
+        if (int rc = refuse_under_capture(s, "a separable convolution of more than 255 taps on this route (the taps are uploaded from host memory)")) return rc;
     Temp *temp = nullptr;
     if (int rc = scratch_alloc((void **)&temp, temp_bytes, s)) return rc;
     TapsBig tx{}, ty{};

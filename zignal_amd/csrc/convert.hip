@@ -347,6 +347,7 @@ static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **o
             }
     }
     if (host_lut) {
+        if (int rc = refuse_under_capture(s, "a caller's sRGB table (srgb_lut, uploaded from host memory)")) return rc;
         if (int rc = scratch_alloc((void **)owned, 256 * sizeof(float), s)) return rc;
         if (int rc = upload_pageable(*owned, host_lut, 256 * sizeof(float), s)) return rc;
         *out = *owned;
@@ -358,6 +359,7 @@ static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **o
     ZG_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(mu);
     if (dev >= 0 && dev < 64 && !per_device[dev]) {
+        if (int rc = refuse_under_capture(s, "the first sRGB conversion on this device (it uploads the library's table)")) return rc;
         float *p = nullptr;
         ZG_HIP(hipMalloc((void **)&p, 256 * sizeof(float)));
         if (int rc = upload_pageable(p, hostmath::srgb_u8_lut(), 256 * sizeof(float), nullptr)) return rc;
@@ -660,6 +662,9 @@ int zg_devmath_apply(int fn, const float *x_dev, const float *y_dev, float *out_
 
 int zg_resize_convert(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const zg_method *method, const float *srgb_lut,
                       zg_stream stream) {
+    // a caller's table is uploaded by the convert half, after the resize half may have been enqueued: refused up front
+    if ((srgb_lut || (method && method->lanczos_lut)) && refuse_under_capture(as_stream(stream), "zg_resize_convert with a caller's sRGB or Lanczos table"))
+        return ZG_ERR_UNSUPPORTED;
     return resize_convert_impl(src, src_space, dst, dst_space, method, srgb_lut, as_stream(stream));
 }
 int zg_resize_convert_host(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const zg_method *method, const float *srgb_lut) {

@@ -1306,7 +1306,7 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
         }
     }
     if (rc == ZG_OK) {
-        if (!bytes && hipMemsetAsync(hist, 0, SC_HIST_COPIES * 256 * sizeof(unsigned int), s) != hipSuccess) rc = ZG_ERR_HIP; // (k_sc_bli4 cleared it otherwise)
+        if (!bytes) rc = fill_async(hist, 0, SC_HIST_COPIES * 256 * sizeof(unsigned int), s); // (k_sc_bli4 cleared it otherwise)
         if (counted)
             hipLaunchKernelGGL((k_sc_gradient<true, true>), dim3(ceil_div(cols, 64), ceil_div(rows, 64)), dim3(256), 0, s, (const uint8_t *)cand, (const float *)sat_g, (const float *)cnt8, (const float *)sat_gm, grad, hist,
                                (int)rows, (int)cols, (int)(window_size / 2));

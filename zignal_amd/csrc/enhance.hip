@@ -102,7 +102,7 @@ static int enhance_impl(const zg_image *img, bool equalize, float cutoff, hipStr
     if ((rc = scratch_alloc((void **)&scratch, 4 * 256 * sizeof(unsigned int) + 4 * 256, s))) return rc;
     unsigned int *hist = (unsigned int *)scratch;
     uint8_t *lut = (uint8_t *)(hist + 4 * 256);
-    if (hipMemsetAsync(hist, 0, 4 * 256 * sizeof(unsigned int), s) != hipSuccess) { scratch_free(scratch, s); ZG_HIP(hipErrorUnknown); }
+    if ((rc = fill_async(hist, 0, 4 * 256 * sizeof(unsigned int), s))) { scratch_free(scratch, s); return rc; }
     rc = dispatch_pixel(img->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         if constexpr (!std::is_same<typename Px<PIX>::Elem, float>::value) {

@@ -426,9 +426,8 @@ int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uin
         J.score = (uint16_t *)(scratch + off[i]);
         J.counts = (uint32_t *)(scratch + off[i] + align256((size_t)J.ih * J.iw * sizeof(uint16_t)));
     }
-    hipError_t e = hipMemsetAsync(scratch + minrc_bytes, 0, gtot_words * sizeof(uint32_t), s);
-    if (e == hipSuccess && nms) e = hipMemsetAsync(scratch, 0xFF, (size_t)n * 2 * sizeof(uint32_t), s);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync", __FILE__, __LINE__);
+    rc = fill_async(scratch + minrc_bytes, 0, gtot_words * sizeof(uint32_t), s);
+    if (rc == ZG_OK && nms) rc = fill_async(scratch, 0xFF, (size_t)n * 2 * sizeof(uint32_t), s);
     for (uint32_t g = 0; g < n && rc == ZG_OK; g += FAST_MAX_JOBS) {
         FastBatch b{};
         b.n = (int32_t)std::min<uint32_t>(FAST_MAX_JOBS, n - g);

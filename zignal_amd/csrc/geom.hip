@@ -128,6 +128,7 @@ struct LutHolder {
 static int device_lanczos_lut(const zg_method *method, hipStream_t s, LutHolder &h) {
     if (method->kind != ZG_INTERP_LANCZOS) return ZG_OK;
     if (method->lanczos_lut) {
+        if (int rc = refuse_under_capture(s, "a caller's Lanczos table (zg_method.lanczos_lut, uploaded from host memory)")) return rc;
         if (int rc = scratch_alloc((void **)&h.owned, 1025 * sizeof(float), s)) return rc;
         if (int rc = upload_pageable(h.owned, method->lanczos_lut, 1025 * sizeof(float), s)) return rc; // the caller's table may be pageable / short-lived
         h.dev = h.owned;
@@ -139,6 +140,7 @@ static int device_lanczos_lut(const zg_method *method, hipStream_t s, LutHolder 
     ZG_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(mu);
     if (dev >= 0 && dev < 64 && !per_device[dev]) {
+        if (int rc = refuse_under_capture(s, "the first Lanczos call on this device (it uploads the library's table)")) return rc;
         float *p = nullptr;
         ZG_HIP(hipMalloc((void **)&p, 1025 * sizeof(float)));
         if (int rc = upload_pageable(p, hostmath::lanczos3_lut(), 1025 * sizeof(float), nullptr)) return rc;
@@ -881,7 +883,7 @@ static int insert_impl(const zg_image *self, const zg_image *source, const float
         q.mask = (uint8_t *)(scratch + samples_bytes);
         q.mask_w = bw;
         q.blend = 0;
-        if (hipMemsetAsync(q.mask, 0, (size_t)bw * bh, s) != hipSuccess) { scratch_free(scratch, s); release_lut(lut, s); ZG_HIP(hipErrorUnknown); }
+        if ((rc = fill_async(q.mask, 0, (size_t)bw * bh, s))) { scratch_free(scratch, s); release_lut(lut, s); return rc; }
         // a view of the scratch addressed with self's coordinates: pixel (min_r, min_c) is scratch[0], row pitch = box width
         target.pixel = source->pixel;
         target.stride = (size_t)bw;

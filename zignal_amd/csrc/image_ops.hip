@@ -5,6 +5,7 @@
 //   flipLeftRight / flipTopBottom   reference src/image/transforms.zig:28-44 (in place)
 // All bit-exact by construction.
 #include "zg_common.h"
+#include <algorithm>
 #include <cstring>
 
 namespace zg {
@@ -130,6 +131,26 @@ static int invert_impl(const zg_image *img, hipStream_t s) {
         ZG_HIP(hipGetLastError());
         return ZG_OK;
     });
+}
+
+// Byte fill on the stream by a kernel. The library clears its device counters and masks with this, not hipMemsetAsync: with the HIP runtime
+// that PyTorch 2.10 (ROCm 7.0) bundles, a captured graph of one hipMemsetAsync and one histogram kernel replayed with wrong counts from the
+// second replay on (the first such graph of a process; the same program under the system runtime was right every time), and the graph
+// replays of autocontrast / equalize and FAST went wrong the same way (tests/test_gpu_graph_replay.py). A kernel node clears at every replay.
+__global__ __launch_bounds__(256) void k_fill(uint8_t *p, uint32_t word, size_t words, size_t bytes) {
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += step) ((uint32_t *)p)[i] = word;
+    for (size_t i = words * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < bytes; i += step) p[i] = (uint8_t)word;
+}
+
+int fill_async(void *p, uint8_t value, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return ZG_OK;
+    const size_t words = ((uintptr_t)p & 3) ? 0 : bytes / 4;
+    const uint32_t word = 0x01010101u * value;
+    const size_t blocks = std::min<size_t>(1024, std::max<size_t>(1, (std::max(words, bytes - words * 4) + 255) / 256));
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)blocks), dim3(256), 0, s, (uint8_t *)p, word, words, bytes);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
 }
 
 } // namespace zg

@@ -1392,6 +1392,7 @@ void zg_jpeg_default_encode_options(zg_jpeg_encode_options *o) { // EncodeOption
     o->comment_len = 0;
 }
 int zg_jpeg_encode(const zg_image *src, int src_space, const zg_jpeg_encode_options *options, uint8_t **out, size_t *out_len, zg_stream stream) {
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_jpeg_encode (it synchronises the stream)")) return rc;
     return no_throw([&] { return encode_impl(src, src_space, options, out, out_len, as_stream(stream)); });
 }
 int zg_jpeg_encode_host(const zg_image *src, int src_space, const zg_jpeg_encode_options *options, uint8_t **out, size_t *out_len) {
@@ -1477,6 +1478,7 @@ int zg_jpeg_coefficient_hash(const uint8_t *jpeg, size_t len, const zg_jpeg_limi
     });
 }
 int zg_jpeg_decode(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits, const zg_image *dst, int dst_space, int *scan_limit_reached_out, zg_stream stream) {
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_jpeg_decode (it uploads coefficients from host memory)")) return rc;
     return no_throw([&] { return decode_impl(jpeg, len, limits, dst, dst_space, scan_limit_reached_out, as_stream(stream)); });
 }
 int zg_jpeg_decode_host(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits, const zg_image *dst, int dst_space, int *scan_limit_reached_out) {

@@ -1002,6 +1002,7 @@ int zg_png_scan_hash(const uint8_t *png, size_t len, const zg_png_limits *limits
     });
 }
 int zg_png_decode(const uint8_t *png, size_t len, const zg_png_limits *limits, const zg_image *dst, int dst_space, int *truncated_out, zg_stream stream) {
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_png_decode (it uploads scanlines from host memory)")) return rc;
     return no_throw([&] { return decode_impl(png, len, limits, dst, dst_space, truncated_out, as_stream(stream)); });
 }
 int zg_png_decode_host(const uint8_t *png, size_t len, const zg_png_limits *limits, const zg_image *dst, int dst_space, int *truncated_out) {
@@ -1014,6 +1015,7 @@ int zg_png_decode_host(const uint8_t *png, size_t len, const zg_png_limits *limi
 }
 int zg_png_filter(const zg_image *src, int filter, uint8_t *filtered, zg_stream stream) { return filter_impl(src, filter, filtered, as_stream(stream)); }
 int zg_png_encode(const zg_image *src, int src_space, const zg_png_encode_options *options, uint8_t **out, size_t *out_len, zg_stream stream) {
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_png_encode (it synchronises the stream)")) return rc;
     return no_throw([&] { return encode_impl(src, src_space, options, out, out_len, as_stream(stream)); });
 }
 int zg_png_encode_host(const zg_image *src, int src_space, const zg_png_encode_options *options, uint8_t **out, size_t *out_len) {

@@ -282,11 +282,14 @@ static void build_axis(int kind, uint32_t src_n, uint32_t dst_n, int taps, std::
 }
 
 // Device-resident tables, cached per (device, kind, src_n, dst_n): repeated resizes of the same geometry
-// (video frames, batches) upload nothing and are graph-capturable after the first call.
+// (video frames, batches) upload nothing and are graph-capturable once the geometry is cached (a miss under capture is refused:
+// building a table is a synchronous upload).
 // Lifetime: the cache and every caller that has fetched a table share ownership (shared_ptr). The cache is LRU (a hit
 // moves the entry to the back), eviction only drops the cache's reference, and a caller keeps its reference until its
 // kernel has been launched — so a table that a launch still points at is never freed under it, whatever other host
-// threads insert meanwhile. The last owner's release is a hipFree, which waits for the device: a kernel already in
+// threads insert meanwhile. Under stream capture the kernel node keeps pointing at the table for as long as the graph lives, so
+// the capture takes a reference of its own (graph_keep), released with the graph's scratch (zg_graph_destroy,
+// zg_release_graph_scratch). The last owner's release is a hipFree, which waits for the device: a kernel already in
 // flight finishes before the memory goes away.
 struct AxisBuf {
     int32_t *dev = nullptr;
@@ -298,7 +301,7 @@ static std::mutex g_cache_mu;
 static std::map<AxisKey, std::pair<std::shared_ptr<AxisBuf>, std::list<AxisKey>::iterator>> g_cache;
 static std::list<AxisKey> g_cache_order; // least recently used first
 
-static int axis_table(int kind, uint32_t src_n, uint32_t dst_n, int taps, AxisTable &out, std::shared_ptr<AxisBuf> &hold) {
+static int axis_table(int kind, uint32_t src_n, uint32_t dst_n, int taps, AxisTable &out, std::shared_ptr<AxisBuf> &hold, hipStream_t s) {
     int dev = 0;
     ZG_HIP(hipGetDevice(&dev));
     const AxisKey key = std::make_tuple(dev, kind, src_n, dst_n);
@@ -310,6 +313,7 @@ static int axis_table(int kind, uint32_t src_n, uint32_t dst_n, int taps, AxisTa
             g_cache_order.splice(g_cache_order.end(), g_cache_order, it->second.second); // most recently used
             hold = it->second.first;
         } else {
+            if (int rc = refuse_under_capture(s, "a Lanczos resize of Rgb(u8) / Rgba(u8) to a geometry not resized before (its table upload)")) return rc;
             std::vector<int32_t> idx, w;
             build_axis(kind, src_n, dst_n, taps, idx, w);
             auto buf = std::make_shared<AxisBuf>(); // frees its device block on every error path below
@@ -328,6 +332,7 @@ static int axis_table(int kind, uint32_t src_n, uint32_t dst_n, int taps, AxisTa
             hold = buf;
         }
     }
+    graph_keep(s, hold); // a captured kernel reads the table at every replay
     out.idx = hold->dev;
     out.w = hold->dev + hold->n;
     return ZG_OK;
@@ -471,8 +476,8 @@ int resize_planes_frames(const zg_image *src, const zg_image *dst, const zg_meth
     std::shared_ptr<AxisBuf> hold_x, hold_y; // keep both tables alive until the kernel below has been launched
     int rc;
     if (kind == ZG_INTERP_LANCZOS) { // the only kernel whose weights need a transcendental: tables from the host
-        if ((rc = axis_table(kind, src->cols, dst->cols, taps, tx, hold_x))) return rc;
-        if ((rc = axis_table(kind, src->rows, dst->rows, taps, ty, hold_y))) return rc;
+        if ((rc = axis_table(kind, src->cols, dst->cols, taps, tx, hold_x, s))) return rc;
+        if ((rc = axis_table(kind, src->rows, dst->rows, taps, ty, hold_y, s))) return rc;
     }
     if (src->pixel == ZG_PIXEL_RGB_U8) return resize_planes_pix<ZG_PIXEL_RGB_U8>(src, dst, kind, tx, ty, n, fr, s);
     return resize_planes_pix<ZG_PIXEL_RGBA_U8>(src, dst, kind, tx, ty, n, fr, s);
@@ -490,6 +495,7 @@ void lanczos_plane_weights(uint32_t src_n, uint32_t dst_n, float *w) {
 // resizePlaneLanczosU8 with caller-made weights: the taps' source indices are the library's (integer arithmetic), the
 // weights are whatever the caller's @sin produced. Tables go up per call (KBs), outside the geometry cache.
 int resize_lanczos_weights_impl(const zg_image *src, const zg_image *dst, const float *wx, const float *wy, hipStream_t s) {
+    if (int rc = refuse_under_capture(s, "zg_resize_lanczos_weights (its tables are uploaded from host memory)")) return rc;
     const size_t nx = (size_t)dst->cols * 6, ny = (size_t)dst->rows * 6;
     std::vector<int32_t> ix, iy, own;
     build_axis(ZG_INTERP_LANCZOS, src->cols, dst->cols, 6, ix, own);

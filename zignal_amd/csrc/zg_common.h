@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <functional>
+#include <memory>
 #include <string>
 #include <type_traits>
 
@@ -244,5 +245,16 @@ void scratch_free(void *p, hipStream_t s);
 int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, const int32_t *ix, int nkx,
                           const int32_t *iy, int nky, int border, hipStream_t s); // conv_sep_bytes2.hip
 size_t scratch_block_budget(); // bytes one long-lived scratch block may take so that a few of them stay cached (a quarter of the cache limit)
+
+// Graph capture (zg_runtime.cpp). capturing(s): `s` is recording a capture right now. refuse_under_capture: what a call that cannot be
+// recorded (a synchronous upload of short-lived host memory, a value read back to the host, a first-use table) calls before it enqueues
+// anything: ZG_ERR_UNSUPPORTED naming `what` and the capture when `s` is capturing, ZG_OK otherwise. graph_keep: device memory that a
+// kernel captured on `s` points at and that the library would otherwise free later (a cached table) stays alive as long as the graph:
+// released by zg_graph_destroy for zg_graph_end_capture's graphs, by zg_release_graph_scratch for captures ended elsewhere.
+bool capturing(hipStream_t s);
+// `bytes` bytes of device memory at p set to `value` by a kernel on s (image_ops.hip): the library's clears, capturable and replay-safe.
+int fill_async(void *p, uint8_t value, size_t bytes, hipStream_t s);
+int refuse_under_capture(hipStream_t s, const char *what);
+void graph_keep(hipStream_t s, std::shared_ptr<void> hold);
 
 } // namespace zg

@@ -79,10 +79,21 @@ struct GraphBlock {
     hipStream_t stream;
     bool in_use;
 };
+struct GraphHold { // device memory that a captured kernel points at and that the library would otherwise free on its own (graph_keep)
+    std::shared_ptr<void> keep;
+    unsigned long long capture_id;
+    hipStream_t stream;
+};
+struct GraphOwned { // what a graph of zg_graph_end_capture keeps until zg_graph_destroy
+    std::vector<void *> blocks;              // scratch blocks its capture took
+    std::vector<std::shared_ptr<void>> holds; // tables its kernels read
+};
 std::mutex g_scratch_mu;
 std::vector<CachedBlock> g_scratch_free;                           // oldest first
 size_t g_scratch_cached_bytes = 0;                                 // sum over g_scratch_free
-std::unordered_map<void *, std::vector<void *>> g_graph_owned;     // zg_graph -> the scratch blocks its capture took
+std::unordered_map<void *, GraphOwned> g_graph_owned;              // zg_graph -> what its capture took
+std::vector<GraphHold> g_graph_holds;                              // holds of captures not handed to a graph (yet)
+std::unordered_map<hipStream_t, unsigned long long> g_own_captures; // stream -> the capture zg_graph_begin_capture started on it
 
 // Idle blocks are kept up to this many bytes (ZIGNAL_HIP_SCRATCH_CACHE_MB, default 2048): enough for the temp planes of a few 4096^2
 // calls in flight, small against 288 GB, and a bound — the host-pointer layer stages whole frames through this cache, and a process
@@ -133,6 +144,14 @@ void release_blocks(std::vector<CachedBlock> &drop) {
     RelaxedCapture relaxed;
     release_blocks_impl(drop);
 }
+// Graph-owned memory going back: the blocks to the driver, the holds dropped (the last owner of a table frees it). hipFree waits for
+// a replay that is still running.
+void release_graph_memory(const std::vector<void *> &blocks, std::vector<std::shared_ptr<void>> &holds) {
+    if (blocks.empty() && holds.empty()) return;
+    RelaxedCapture relaxed;
+    for (void *p : blocks) (void)hipFree(p);
+    holds.clear();
+}
 // Oldest idle blocks out until the cache holds at most `limit` bytes and 64 blocks. Called where the caller is about to pay a
 // hipMalloc anyway (a cache miss) and from scratch_free only past TWICE the limit: freeing is a device-wide synchronisation, and a
 // steady state whose working set sits a little above the limit (the pipeline's two ping-pong blocks plus a table) must not pay one
@@ -178,6 +197,27 @@ int scratch_alloc_captured(void **out, size_t need, int dev, unsigned long long 
     return ZG_OK;
 }
 } // namespace
+
+bool capturing(hipStream_t s) {
+    unsigned long long id = 0;
+    return stream_capture_id(s, &id);
+}
+
+// The one gate of every call that cannot be recorded into a graph: it runs before the call enqueues anything, so the capture stays
+// valid (the graph simply lacks the refused call) and the stream is usable as soon as the capture ends.
+int refuse_under_capture(hipStream_t s, const char *what) {
+    unsigned long long id = 0;
+    if (!stream_capture_id(s, &id)) return ZG_OK;
+    set_error("%s cannot be recorded into a graph: stream %p is capturing (capture %llu); the call was refused", what, (void *)s, id);
+    return ZG_ERR_UNSUPPORTED;
+}
+
+void graph_keep(hipStream_t s, std::shared_ptr<void> hold) {
+    unsigned long long id = 0;
+    if (!hold || !stream_capture_id(s, &id)) return;
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    g_graph_holds.push_back(GraphHold{std::move(hold), id, s});
+}
 
 int scratch_alloc(void **out, size_t bytes, hipStream_t s) {
     *out = nullptr;
@@ -269,26 +309,32 @@ int host_threads() {
 }
 
 // Pageable host memory <-> device memory, synchronised before returning (the callers' host buffers are short-lived).
+// A capture cannot record these (the host side is short-lived, and the synchronisation is illegal inside a capture): the entry points
+// that reach them refuse first (refuse_under_capture); the checks here are the backstop.
 int upload_pageable_rows(void *dst_dev, const void *src_host, size_t spitch, size_t width, size_t rows, hipStream_t s) {
     if (width == 0 || rows == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(s, "an upload from pageable host memory")) return rc;
     ZG_HIP(hipMemcpy2DAsync(dst_dev, width, src_host, spitch, width, rows, hipMemcpyHostToDevice, s));
     ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
 }
 int upload_pageable(void *dst_dev, const void *src_host, size_t bytes, hipStream_t s) {
     if (bytes == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(s, "an upload from pageable host memory")) return rc;
     ZG_HIP(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, s));
     ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
 }
 int download_pageable_rows(void *dst_host, size_t dpitch, const void *src_dev, size_t width, size_t rows, hipStream_t s) {
     if (width == 0 || rows == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(s, "a download to host memory")) return rc;
     ZG_HIP(hipMemcpy2DAsync(dst_host, dpitch, src_dev, width, width, rows, hipMemcpyDeviceToHost, s));
     ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
 }
 int download_pageable(void *dst_host, const void *src_dev, size_t bytes, hipStream_t s) {
     if (bytes == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(s, "a download to host memory")) return rc;
     ZG_HIP(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, s));
     ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
@@ -606,11 +652,13 @@ int zg_free_host(void *host_ptr) {
 
 int zg_memcpy_h2d(void *dst_dev, const void *src_host, size_t bytes, zg_stream stream) {
     if (bytes == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_memcpy_h2d (it synchronises the stream; zg_memcpy_h2d_async is capturable)")) return rc;
     return upload_pageable(dst_dev, src_host, bytes, as_stream(stream));
 }
 
 int zg_memcpy_d2h(void *dst_host, const void *src_dev, size_t bytes, zg_stream stream) {
     if (bytes == 0) return ZG_OK;
+    if (int rc = refuse_under_capture(as_stream(stream), "zg_memcpy_d2h (it synchronises the stream; zg_memcpy_d2h_async is capturable)")) return rc;
     return download_pageable(dst_host, src_dev, bytes, as_stream(stream));
 }
 
@@ -633,6 +681,7 @@ int zg_image_upload(const zg_image *dst_dev, const zg_image *src_host, zg_stream
                src_host->rows, src_host->cols, dst_dev->rows, dst_dev->cols);
     ZG_REQUIRE(dst_dev->pixel == src_host->pixel, ZG_ERR_INVALID_ARGUMENT, "upload: pixel types differ");
     if (dst_dev->rows == 0 || dst_dev->cols == 0) return ZG_OK;
+    if ((rc = refuse_under_capture(as_stream(stream), "zg_image_upload (it synchronises the stream)"))) return rc;
     const size_t ps = pixel_size(dst_dev->pixel);
     ZG_HIP(hipMemcpy2DAsync(dst_dev->data, dst_dev->stride * ps, src_host->data, src_host->stride * ps, (size_t)dst_dev->cols * ps, dst_dev->rows,
                             hipMemcpyHostToDevice, as_stream(stream)));
@@ -647,6 +696,7 @@ int zg_image_download(const zg_image *dst_host, const zg_image *src_dev, zg_stre
                src_dev->rows, src_dev->cols, dst_host->rows, dst_host->cols);
     ZG_REQUIRE(dst_host->pixel == src_dev->pixel, ZG_ERR_INVALID_ARGUMENT, "download: pixel types differ");
     if (dst_host->rows == 0 || dst_host->cols == 0) return ZG_OK;
+    if ((rc = refuse_under_capture(as_stream(stream), "zg_image_download (it synchronises the stream)"))) return rc;
     const size_t ps = pixel_size(dst_host->pixel);
     ZG_HIP(hipMemcpy2DAsync(dst_host->data, dst_host->stride * ps, src_dev->data, src_dev->stride * ps, (size_t)dst_host->cols * ps, dst_host->rows,
                             hipMemcpyDeviceToHost, as_stream(stream)));
@@ -714,36 +764,72 @@ int zg_stream_wait_event(zg_stream s, zg_event e) {
 int zg_graph_begin_capture(zg_stream stream) {
     ZG_REQUIRE(stream, ZG_ERR_INVALID_ARGUMENT, "zg_graph_begin_capture: the default stream cannot be captured; create one with zg_stream_create");
     ZG_HIP(hipStreamBeginCapture(as_stream(stream), hipStreamCaptureModeThreadLocal));
+    unsigned long long id = 0;
+    if (stream_capture_id(as_stream(stream), &id)) { // remembered here: a capture that a refused call invalidated reports no id at its end
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        g_own_captures[as_stream(stream)] = id;
+    }
     return ZG_OK;
 }
 
 int zg_graph_end_capture(zg_stream stream, zg_graph *out) {
     ZG_REQUIRE(stream && out, ZG_ERR_INVALID_ARGUMENT, "zg_graph_end_capture: null argument");
     *out = nullptr;
-    unsigned long long capture_id = 0;
-    const bool capturing = stream_capture_id(as_stream(stream), &capture_id);
+    const hipStream_t s = as_stream(stream);
+    // the live id of an active capture; the one remembered at zg_graph_begin_capture only when the capture no longer reports one (a call
+    // invalidated it). A remembered entry may be stale (a capture begun here but ended by the caller's own hipStreamEndCapture): never
+    // preferred to the live id.
+    unsigned long long capture_id = 0, remembered = 0;
+    bool known = stream_capture_id(s, &capture_id), had = false;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        auto it = g_own_captures.find(s);
+        if (it != g_own_captures.end()) {
+            remembered = it->second;
+            had = true;
+            g_own_captures.erase(it);
+        }
+    }
+    if (!known && had) {
+        capture_id = remembered;
+        known = true;
+    }
     hipGraph_t g = nullptr;
-    ZG_HIP(hipStreamEndCapture(as_stream(stream), &g));
+    hipError_t e = hipStreamEndCapture(s, &g);
+    const char *what = "hipStreamEndCapture";
     hipGraphExec_t exec = nullptr;
-    const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    // the scratch this capture took now belongs to the graph (or goes back at once if there is no graph to own it)
-    std::vector<void *> mine;
-    if (capturing) {
+    if (e == hipSuccess) {
+        e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+        what = "hipGraphInstantiate";
+    }
+    if (g) (void)hipGraphDestroy(g);
+    // the scratch and the tables this capture took now belong to the graph, or go back at once if there is no graph to own them
+    // (a failed end or instantiation included)
+    GraphOwned mine;
+    if (known) {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         for (size_t i = 0; i < g_graph_blocks.size();) {
             if (g_graph_blocks[i].capture_id == capture_id) {
-                mine.push_back(g_graph_blocks[i].p);
+                mine.blocks.push_back(g_graph_blocks[i].p);
                 g_graph_blocks.erase(g_graph_blocks.begin() + (long)i);
             } else {
                 ++i;
             }
         }
-        if (e == hipSuccess && !mine.empty()) g_graph_owned[(void *)exec] = mine;
+        for (size_t i = 0; i < g_graph_holds.size();) {
+            if (g_graph_holds[i].capture_id == capture_id) {
+                mine.holds.push_back(std::move(g_graph_holds[i].keep));
+                g_graph_holds.erase(g_graph_holds.begin() + (long)i);
+            } else {
+                ++i;
+            }
+        }
+        if (e == hipSuccess && (!mine.blocks.empty() || !mine.holds.empty())) g_graph_owned[(void *)exec] = std::move(mine);
     }
-    if (e != hipSuccess)
-        for (void *p : mine) (void)hipFree(p);
-    ZG_HIP(e);
+    if (e != hipSuccess) {
+        release_graph_memory(mine.blocks, mine.holds);
+        return hip_fail(e, what, __FILE__, __LINE__);
+    }
     *out = (zg_graph)exec;
     return ZG_OK;
 }
@@ -756,27 +842,28 @@ int zg_graph_launch(zg_graph graph, zg_stream stream) {
 
 int zg_graph_destroy(zg_graph graph) {
     if (!graph) return ZG_OK;
-    std::vector<void *> mine;
+    GraphOwned mine;
     {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         auto it = g_graph_owned.find((void *)graph);
         if (it != g_graph_owned.end()) {
-            mine.swap(it->second);
+            mine = std::move(it->second);
             g_graph_owned.erase(it);
         }
     }
     const hipError_t e = hipGraphExecDestroy((hipGraphExec_t)graph);
-    for (void *p : mine) (void)hipFree(p); // hipFree waits for a replay that is still running
+    release_graph_memory(mine.blocks, mine.holds);
     ZG_HIP(e);
     return ZG_OK;
 }
 
-// Scratch of captures the library did not end itself (torch.cuda.graph around Image calls, a caller's own hipStreamEndCapture):
-// nobody tells the library when those graphs die, so their blocks stay reserved until the caller says so here — once the graphs
-// are destroyed (hipFree waits for whatever is still running). Graphs made with zg_graph_end_capture own their scratch and are
-// not touched; neither are blocks of a capture that is still in progress or of a call that is still running.
+// Scratch and tables of captures the library did not end itself (torch.cuda.graph around Image calls, a caller's own hipStreamEndCapture):
+// nobody tells the library when those graphs die, so they stay reserved until the caller says so here — once the graphs are destroyed
+// (hipFree waits for whatever is still running). Graphs made with zg_graph_end_capture own theirs and are not touched; neither are those
+// of a capture that is still in progress or of a call that is still running.
 int zg_release_graph_scratch(void) {
-    std::vector<GraphBlock> drop;
+    std::vector<void *> blocks;
+    std::vector<std::shared_ptr<void>> holds;
     {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         for (size_t i = 0; i < g_graph_blocks.size();) {
@@ -787,11 +874,20 @@ int zg_release_graph_scratch(void) {
                 ++i;
                 continue;
             }
-            drop.push_back(g);
+            blocks.push_back(g.p);
             g_graph_blocks.erase(g_graph_blocks.begin() + (long)i);
         }
+        for (size_t i = 0; i < g_graph_holds.size();) {
+            unsigned long long id = 0;
+            if (stream_capture_id(g_graph_holds[i].stream, &id) && id == g_graph_holds[i].capture_id) {
+                ++i;
+                continue;
+            }
+            holds.push_back(std::move(g_graph_holds[i].keep));
+            g_graph_holds.erase(g_graph_holds.begin() + (long)i);
+        }
     }
-    for (const GraphBlock &g : drop) ZG_HIP(hipFree(g.p));
+    release_graph_memory(blocks, holds);
     return ZG_OK;
 }
 
