@@ -182,7 +182,9 @@ ZG_API int zg_event_elapsed_ms(zg_event start, zg_event stop, float *ms); /* dev
  *   conversion of u8 pixels that needs the sRGB table (to Xyz, Oklab or a float-only space), and a Lanczos resize of Rgb(u8)
  *   / Rgba(u8) to a geometry that is not among the last 64 resized. Make one such call outside the capture first. In a
  *   multi-step call (zg_resize_convert, zg_batch_pipeline, zg_pyramid_build) a first-use refusal can come after earlier steps
- *   were recorded: discard that capture. */
+ *   were recorded: discard that capture.
+ * zg_graph_begin_capture waits for the work already queued on `stream` (other threads may then run eager calls during the
+ * capture: none of them meets an event of the capturing stream). */
 ZG_API int zg_graph_begin_capture(zg_stream stream);
 ZG_API int zg_graph_end_capture(zg_stream stream, zg_graph *out);
 ZG_API int zg_graph_launch(zg_graph graph, zg_stream stream);

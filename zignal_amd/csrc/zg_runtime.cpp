@@ -109,8 +109,10 @@ size_t scratch_cache_limit() {
 void release_blocks(std::vector<CachedBlock> &drop); // defined below RelaxedCapture
 void release_blocks_impl(std::vector<CachedBlock> &drop) {
     for (const CachedBlock &b : drop) {
-        (void)hipEventSynchronize(b.done);
-        (void)hipEventDestroy(b.done);
+        if (b.done) { // no event: settled by settle_stream_blocks
+            (void)hipEventSynchronize(b.done);
+            (void)hipEventDestroy(b.done);
+        }
         (void)hipFree(b.p);
     }
     drop.clear();
@@ -241,9 +243,11 @@ int scratch_alloc(void **out, size_t bytes, hipStream_t s) {
         }
     }
     if (take.p) {
-        const hipError_t e = take.last != s ? hipStreamWaitEvent(s, take.done, 0) : hipSuccess;
-        if (e != hipSuccess) (void)hipEventSynchronize(take.done); // still ordered, just not asynchronously
-        (void)hipEventDestroy(take.done);
+        if (take.done) { // no event: the block's last use has finished (settle_stream_blocks)
+            const hipError_t e = take.last != s ? hipStreamWaitEvent(s, take.done, 0) : hipSuccess;
+            if (e != hipSuccess) (void)hipEventSynchronize(take.done); // still ordered, just not asynchronously
+            (void)hipEventDestroy(take.done);
+        }
     } else {
         evict_down_to(scratch_cache_limit() > need ? scratch_cache_limit() - need : 0); // make room for the block this call will bring back
         hipError_t e = hipMalloc(&take.p, need);
@@ -293,6 +297,25 @@ void scratch_free(void *p, hipStream_t s) {
         far_over = g_scratch_free.size() > 64 || g_scratch_cached_bytes > 2 * scratch_cache_limit();
     }
     if (far_over) evict_down_to(scratch_cache_limit()); // the hard bound; between the limit and twice the limit the next cache miss trims
+}
+
+// Before a capture begins on `s`: the cached blocks last used on `s` carry events recorded on it, and the runtime takes a wait on, or a
+// query of, an event whose stream is capturing for a part of that capture, from whichever thread it comes: another thread's eager call
+// that took such a block (or evicted it) invalidated the capture. So the stream is drained and those events are dropped; a block
+// without an event is idle. Inside the capture nothing new is recorded for the cache (its blocks are graph-owned).
+static int settle_stream_blocks(hipStream_t s) {
+    ZG_HIP(hipStreamSynchronize(s));
+    std::vector<hipEvent_t> settled;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        for (CachedBlock &b : g_scratch_free)
+            if (b.last == s && b.done) {
+                settled.push_back(b.done);
+                b.done = nullptr;
+            }
+    }
+    for (hipEvent_t e : settled) (void)hipEventDestroy(e);
+    return ZG_OK;
 }
 
 // What one scratch block of a long-lived working set may take so that a few of them stay inside the cache (batch.hip's ping-pong blocks).
@@ -763,6 +786,7 @@ int zg_stream_wait_event(zg_stream s, zg_event e) {
 // work of a call (taps, tables, argument checks) happens at capture time and is baked in.
 int zg_graph_begin_capture(zg_stream stream) {
     ZG_REQUIRE(stream, ZG_ERR_INVALID_ARGUMENT, "zg_graph_begin_capture: the default stream cannot be captured; create one with zg_stream_create");
+    if (int rc = settle_stream_blocks(as_stream(stream))) return rc; // other threads' eager calls must not meet this stream's events during the capture
     ZG_HIP(hipStreamBeginCapture(as_stream(stream), hipStreamCaptureModeThreadLocal));
     unsigned long long id = 0;
     if (stream_capture_id(as_stream(stream), &id)) { // remembered here: a capture that a refused call invalidated reports no id at its end
