@@ -721,4 +721,9 @@ ZG_API void zg_jpeg_free(void *p);
 #ifdef __cplusplus
 }
 #endif
+
+/* ORB (src/features/orb.zig) on top of the pyramid and FAST above: a module of its own with its own header, bindings table
+ * (zignal_amd/_lib.py: _ORB_SIGNATURES) and Zig file (zig/zignal_hip_orb.zig). */
+#include "zignal_hip_orb.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -20,6 +20,8 @@
 //!   gaussian_taps           gaussianBlur's normalised taps for a sigma sweep   src/image.zig:973-990
 //!   lanczos_plane_weights   resizePlaneLanczosU8's six weights per destination column, 4096 -> 1500 and 640 -> 1000   src/image/channel_ops.zig:446-466
 //!   oklab_17 / lab_17       Rgb(u8) on the 17^3 lattice {0, 16, ..., 240, 255}^3 -> Oklab(f32) / Lab(f32)   src/color.zig:1261-1272, 1289-1310, 1381-1400
+//!   orb                     ORB's orientation weight table at comptime (961), atan2 in degrees on a sweep [y, x, degrees], cos / sin of
+//!                           degrees on a sweep [degrees, cos, sin]             src/features/orb.zig:340-357, 424-425, 432-433
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
@@ -181,6 +183,23 @@ fn fPowInv24(x: f32) f32 {
     return pow(f32, x, 1.0 / srgb_gamma_exponent);
 }
 
+/// src/features/orb.zig:340-357: exp(-d^2 / (225 / 2)) inside d^2 <= 225, at comptime
+const orb_weights: [31 * 31]f32 = blk: {
+    @setEvalBranchQuota(100_000);
+    var vals: [31 * 31]f32 = @splat(0);
+    const radius_sq: f32 = 225.0;
+    const denom: f32 = radius_sq / 2.0;
+    for (0..31) |v| {
+        for (0..31) |u| {
+            const dy: i32 = @as(i32, @intCast(v)) - 15;
+            const dx: i32 = @as(i32, @intCast(u)) - 15;
+            const dist_sq: f32 = @floatFromInt(dx * dx + dy * dy);
+            if (dist_sq <= radius_sq) vals[v * 31 + u] = @exp(-dist_sq / denom);
+        }
+    }
+    break :blk vals;
+};
+
 pub fn main(init: std.process.Init) !void {
     var buffer: [1 << 16]u8 = undefined;
     var stdout = std.Io.File.stdout().writer(init.io, &buffer);
@@ -267,7 +286,33 @@ pub fn main(init: std.process.Init) !void {
     try sweep(w, "cbrt", fCbrt, 14, 0.0, 1.2, 4096, false);
     try sweep(w, "pow24", fPow24, 15, 0.0404, 1.0, 4096, false);
     try sweep(w, "pow_third", fPowThird, 16, 0.008856, 1.1, 4096, false);
-    try sweep(w, "pow_inv24", fPowInv24, 17, 0.0031308, 1.0, 4096, true);
+    try sweep(w, "pow_inv24", fPowInv24, 17, 0.0031308, 1.0, 4096, false);
+
+    // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
+    // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])
+    try w.print("  \"orb\": {{\"weights\": [", .{});
+    for (orb_weights, 0..) |v, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", bits(v) });
+    try w.print("], \"atan2_degrees\": [", .{});
+    {
+        var rng = Lcg{ .s = 18 };
+        for (0..4096) |i| {
+            const y = runtime(rng.uniform(-15.0, 15.0));
+            const x = runtime(rng.uniform(-15.0, 15.0));
+            const deg = std.math.radiansToDegrees(std.math.atan2(y, x));
+            try w.print("{s}[{d},{d},{d}]", .{ if (i == 0) "" else ",", bits(y), bits(x), bits(deg) });
+        }
+    }
+    try w.print("], \"cos_sin_of_degrees\": [", .{});
+    {
+        var rng = Lcg{ .s = 19 };
+        for (0..4096) |i| {
+            const a = runtime(rng.uniform(-180.0, 180.0));
+            const c = @cos(std.math.degreesToRadians(a));
+            const sn = @sin(std.math.degreesToRadians(a));
+            try w.print("{s}[{d},{d},{d}]", .{ if (i == 0) "" else ",", bits(a), bits(c), bits(sn) });
+        }
+    }
+    try w.print("]}}\n", .{});
     try w.print("}}\n", .{});
     try w.flush();
 }

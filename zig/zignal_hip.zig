@@ -309,7 +309,7 @@ fn pixelOf(comptime T: type) Pixel {
     };
 }
 
-fn check(status: c_int) !void {
+pub fn check(status: c_int) !void {
     return switch (status) {
         0 => {},
         1 => error.DimensionMismatch,

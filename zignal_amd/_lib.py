@@ -87,6 +87,21 @@ class ZgKeypoint(C.Structure):
                 ("octave", C.c_int32), ("class_id", C.c_int32)]
 
 
+class ZgBinaryDescriptor(C.Structure):
+    """zg_binary_descriptor == BinaryDescriptor (src/features/BinaryDescriptor.zig:10)."""
+    _fields_ = [("bits", C.c_uint8 * 32)]
+
+
+class ZgOrbParams(C.Structure):
+    """zg_orb_params == Orb's fields (src/features/orb.zig:87-109) and the optional orientation weight table."""
+    _fields_ = [("n_features", C.c_uint32), ("scale_factor", C.c_float), ("n_levels", C.c_uint32), ("edge_threshold", C.c_uint32),
+                ("first_level", C.c_uint32), ("wta_k", C.c_uint32), ("fast_threshold", C.c_uint32), ("score_type", C.c_int32),
+                ("orientation_weights", C.c_void_p)]
+
+
+ORB_HARRIS_SCORE, ORB_FAST_SCORE = range(2)
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -273,6 +288,19 @@ _RESTYPES = {"zg_last_error": C.c_char_p, "zg_shutdown": None, "zg_pixel_size": 
 # every symbol include/zignal_hip.h declares; tests check the library exports all of them
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# the ORB module: every symbol include/zignal_hip_orb.h declares
+_ORB_SIGNATURES = {
+    "zg_orb_default_params": [C.POINTER(ZgOrbParams)],
+    "zg_orb_features_per_level": [C.POINTER(ZgOrbParams), _U32P],
+    "zg_orb_adaptive_threshold": [C.POINTER(ZgOrbParams), C.c_uint32],
+    "zg_orb_detect_and_compute": [_IMG, C.POINTER(ZgOrbParams), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_orb_compute": [_IMG, C.POINTER(ZgOrbParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_orb_detect_and_compute_host": [_IMG, C.POINTER(ZgOrbParams), C.c_void_p, C.c_void_p, C.c_uint32, _U32P],
+    "zg_orb_compute_host": [_IMG, C.POINTER(ZgOrbParams), C.c_void_p, C.c_uint32, C.c_void_p],
+}
+_ORB_RESTYPES = {"zg_orb_default_params": None}
+ORB_EXPORTED_SYMBOLS = tuple(_ORB_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -282,10 +310,11 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, argtypes in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if the library does not export it
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
+        for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES)):
+            for name, argtypes in table.items():
+                fn = getattr(l, name)  # AttributeError if the library does not export it
+                fn.argtypes = argtypes
+                fn.restype = restypes.get(name, C.c_int)
         if l.zg_sizeof_step() != C.sizeof(ZgStep):  # zg_step has no size field: a library built from another header must not be handed ZgStep arrays
             raise ImportError(f"{LIB_PATH}: sizeof(zg_step) is {l.zg_sizeof_step()} in the library, {C.sizeof(ZgStep)} in this binding: rebuild the library")
         _lib = l

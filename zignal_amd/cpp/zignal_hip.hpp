@@ -584,4 +584,75 @@ struct Fast {
     }
 };
 
+// ---- features: ORB (src/features/orb.zig, BinaryDescriptor.zig) ----
+using BinaryDescriptor = zg_binary_descriptor; // BinaryDescriptor.zig:10
+static_assert(sizeof(BinaryDescriptor) == 32, "zg_binary_descriptor is BinaryDescriptor's 32 bytes");
+
+// Orb (src/features/orb.zig:87-109): the reference's fields and defaults; keypoints and descriptors in its order, bit for bit.
+struct Orb {
+    enum ScoreType { harris_score = ZG_ORB_HARRIS_SCORE, fast_score = ZG_ORB_FAST_SCORE };
+    size_t n_features = 500;
+    float scale_factor = 1.2f;
+    uint8_t n_levels = 8;
+    uint8_t edge_threshold = 15;
+    uint8_t first_level = 0;
+    uint8_t wta_k = 2;
+    uint8_t fast_threshold = 20;
+    ScoreType score_type = fast_score;
+    const float *orientation_weights = nullptr; // null, or the caller's 31 x 31 table (orb.zig:340-357)
+
+    struct Features {
+        std::vector<KeyPoint> keypoints;
+        std::vector<BinaryDescriptor> descriptors;
+    };
+
+    zg_orb_params params() const {
+        return zg_orb_params{(uint32_t)(n_features > 0xFFFFFFFFu ? 0xFFFFFFFFu : n_features), scale_factor, n_levels, edge_threshold, first_level, wta_k,
+                             fast_threshold, (int32_t)score_type, orientation_weights};
+    }
+    std::vector<uint32_t> featuresPerLevel() const { // orb.zig:279-334
+        const zg_orb_params p = params();
+        std::vector<uint32_t> out(n_levels);
+        check(zg_orb_features_per_level(&p, out.data()));
+        return out;
+    }
+    uint8_t adaptiveThreshold(uint32_t level) const { // orb.zig:511-517
+        const zg_orb_params p = params();
+        const int rc = zg_orb_adaptive_threshold(&p, level);
+        if (rc < 0) check(-rc);
+        return (uint8_t)rc;
+    }
+    // host image (orb.zig:250-276; with_descriptors = false is Orb.detect): the count first, then the arrays
+    Features detectAndCompute(const Image<uint8_t> &image, bool with_descriptors = true) const {
+        const zg_image s = image.desc();
+        const zg_orb_params p = params();
+        uint32_t n = 0;
+        check(zg_orb_detect_and_compute_host(&s, &p, nullptr, nullptr, 0, &n));
+        Features f;
+        f.keypoints.resize(n);
+        if (with_descriptors) f.descriptors.resize(n);
+        if (n) check(zg_orb_detect_and_compute_host(&s, &p, f.keypoints.data(), with_descriptors ? f.descriptors.data() : nullptr, n, &n));
+        return f;
+    }
+    std::vector<KeyPoint> detect(const Image<uint8_t> &image) const { return detectAndCompute(image, false).keypoints; }
+    std::vector<BinaryDescriptor> compute(const Image<uint8_t> &image, const std::vector<KeyPoint> &keypoints) const { // orb.zig:133-144
+        const zg_image s = image.desc();
+        const zg_orb_params p = params();
+        std::vector<BinaryDescriptor> out(keypoints.size());
+        if (!keypoints.empty()) check(zg_orb_compute_host(&s, &p, keypoints.data(), (uint32_t)keypoints.size(), out.data()));
+        return out;
+    }
+    // asynchronous device forms: keypoints / descriptors / count are device memory; *count receives the full length
+    void detectAndComputeInto(const DeviceImage<uint8_t> &image, KeyPoint *keypoints, BinaryDescriptor *descriptors, uint32_t capacity, uint32_t *count) const {
+        const zg_image s = image.desc();
+        const zg_orb_params p = params();
+        check(zg_orb_detect_and_compute(&s, &p, keypoints, descriptors, capacity, count, image.stream()));
+    }
+    void computeInto(const DeviceImage<uint8_t> &image, const KeyPoint *keypoints, uint32_t n, BinaryDescriptor *descriptors) const {
+        const zg_image s = image.desc();
+        const zg_orb_params p = params();
+        check(zg_orb_compute(&s, &p, keypoints, n, descriptors, image.stream()));
+    }
+};
+
 } // namespace zignal

@@ -47,6 +47,7 @@ struct FastJob {
     uint32_t *counts;         // per cell (NMS) or per candidate row
     uint32_t *gtot;           // per group of `group` consecutive cells: the sum of their counts (zeroed before the call)
     zg_keypoint *out;
+    uint32_t *out_pos, *out_key; // the compact list instead of `out` (fast_detect_compact): pixel index row * cols + col, and the score
     uint32_t *count;
     int32_t cells_x, cells_y; // NMS: the cell grid's upper bound; no NMS: 1 x ih (a "cell" per row)
     int32_t tiles_x;          // k_fast_detect workgroups per tile row
@@ -269,6 +270,11 @@ __device__ inline uint32_t cell_offset(const FastJob &J, uint32_t blk, uint32_t 
 
 __device__ inline void write_keypoint(const FastJob &J, uint32_t slot, int row, int col, int score) {
     if (slot >= J.capacity) return;
+    if (J.out_pos) { // uniform over the launch
+        J.out_pos[slot] = (uint32_t)row * (uint32_t)J.cols + (uint32_t)col;
+        J.out_key[slot] = (uint32_t)score;
+        return;
+    }
     zg_keypoint kp;
     kp.x = (float)col;       // KeyPoint.zig:9-28; Fast.zig:56-62
     kp.y = (float)row;
@@ -381,7 +387,8 @@ size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // n independent Fast.detect calls (validated), scratch from the caching allocator, three launches per group of FAST_MAX_JOBS.
 int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t min_contiguous, int nms, zg_keypoint *const *outs,
-             const uint32_t *capacities, uint32_t *const *counts, hipStream_t s) {
+             const uint32_t *capacities, uint32_t *const *counts, hipStream_t s, uint32_t *const *pos_outs = nullptr,
+             uint32_t *const *key_outs = nullptr) {
     std::vector<FastJob> jobs(n);
     // scratch: the minrc words of every job (set to 0xFF), the group totals of every job (zeroed), then per job its score map
     // and cell counts
@@ -399,7 +406,9 @@ int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uin
         J.iw = J.cols - 6;
         J.threshold = thresholds[i];
         J.capacity = capacities[i];
-        J.out = outs[i];
+        J.out = outs ? outs[i] : nullptr;
+        J.out_pos = pos_outs ? pos_outs[i] : nullptr;
+        J.out_key = key_outs ? key_outs[i] : nullptr;
         J.count = counts[i];
         J.cells_y = nms ? (int32_t)ceil_div((unsigned)J.ih, CELL) : J.ih;
         J.cells_x = nms ? (int32_t)ceil_div((unsigned)J.iw, CELL) : 1;
@@ -460,6 +469,14 @@ int check_fast_options(uint32_t threshold, uint32_t min_contiguous) {
 }
 
 } // namespace
+
+// Fast.detect with NMS and min_contiguous 9 on n Image(u8) levels (validated by the caller) for ORB (orb.hip): the same launches and the
+// same list order as zg_fast_detect_batch, each entry as 8 bytes (pixel index row * cols + col in pos, the integer score in key)
+// instead of a 28-byte keypoint, so a list as long as the level has candidates costs 8 bytes a pixel.
+int fast_detect_compact(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t *const *pos, uint32_t *const *key,
+                        const uint32_t *capacities, uint32_t *const *counts, hipStream_t s) {
+    return fast_run(images, n, thresholds, 9, 1, nullptr, capacities, counts, s, pos, key);
+}
 } // namespace zg
 
 using namespace zg;

@@ -226,6 +226,9 @@ int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t sr
 int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int dst_space, uint32_t n, size_t src_frame, size_t dst_frame, const float *srgb_lut,
                                 hipStream_t s);                                                                                                       // convert.hip
 
+int fast_detect_compact(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t *const *pos, uint32_t *const *key,
+                        const uint32_t *capacities, uint32_t *const *counts, hipStream_t s); // fast.hip: FAST for ORB, 8-byte list entries
+
 // u8 separable convolution of a batch of equally sized frames laid out back to back, one wave per column strip
 // (conv_sep_stream.hip). Returns -1 when its preconditions do not hold: the caller falls back to the tiled kernels.
 struct StreamJob {

@@ -874,6 +874,131 @@ class Fast:
             caps = [max(int(c), cap) for c, cap in zip(n, caps)]
 
 
+# BinaryDescriptor (reference src/features/BinaryDescriptor.zig:10) as a numpy structured dtype: the bytes of zg_binary_descriptor.
+BINARY_DESCRIPTOR_DTYPE = np.dtype([("bits", "u1", (32,))])
+BinaryDescriptor = BINARY_DESCRIPTOR_DTYPE
+assert BINARY_DESCRIPTOR_DTYPE.itemsize == C.sizeof(L.ZgBinaryDescriptor)
+
+
+class Orb:
+    """Orb (reference src/features/orb.zig): ORB keypoints and rotated-BRIEF descriptors with the reference's fields and defaults
+    (:87-109). Keypoints come back as a KEYPOINT_DTYPE array and descriptors as a BINARY_DESCRIPTOR_DTYPE array, both in the
+    reference's order, bit for bit. score_type is "fast_score" or "harris_score". orientation_weights: None, or the caller's 31 x 31
+    orientation weight table (961 floats) in place of the library's."""
+
+    SCORE_TYPES = {"harris_score": L.ORB_HARRIS_SCORE, "fast_score": L.ORB_FAST_SCORE}
+
+    def __init__(self, n_features: int = 500, scale_factor: float = 1.2, n_levels: int = 8, edge_threshold: int = 15, first_level: int = 0,
+                 wta_k: int = 2, fast_threshold: int = 20, score_type: str = "fast_score", orientation_weights=None):
+        if score_type not in self.SCORE_TYPES:
+            raise ValueError(f"score_type {score_type!r}: one of {sorted(self.SCORE_TYPES)}")
+        self.n_features, self.scale_factor, self.n_levels = int(n_features), float(scale_factor), int(n_levels)
+        self.edge_threshold, self.first_level, self.wta_k = int(edge_threshold), int(first_level), int(wta_k)
+        self.fast_threshold, self.score_type = int(fast_threshold), score_type
+        self.orientation_weights = None
+        if orientation_weights is not None:
+            self.orientation_weights = np.ascontiguousarray(orientation_weights, np.float32).reshape(-1)
+            if self.orientation_weights.size != 31 * 31:
+                raise ValueError("orientation_weights holds 31 x 31 floats")
+
+    def __repr__(self):
+        return (f"Orb(n_features={self.n_features}, scale_factor={self.scale_factor}, n_levels={self.n_levels}, edge_threshold={self.edge_threshold}, "
+                f"first_level={self.first_level}, wta_k={self.wta_k}, fast_threshold={self.fast_threshold}, score_type={self.score_type!r})")
+
+    def _params(self) -> "L.ZgOrbParams":
+        for name in ("n_features", "n_levels", "edge_threshold", "first_level", "wta_k", "fast_threshold"):
+            if not 0 <= getattr(self, name) < 1 << 32:
+                raise L.InvalidArgument(L.ERR_INVALID_ARGUMENT, f"orb: {name} = {getattr(self, name)}")
+        w = None if self.orientation_weights is None else self.orientation_weights.ctypes.data
+        return L.ZgOrbParams(self.n_features, self.scale_factor, self.n_levels, self.edge_threshold, self.first_level, self.wta_k,
+                             self.fast_threshold, self.SCORE_TYPES[self.score_type], w)
+
+    def features_per_level(self) -> List[int]:
+        """Orb.computeFeaturesPerLevel (:279-334)."""
+        p = self._params()
+        out = (C.c_uint32 * max(self.n_levels, 1))()
+        L.check(L.lib().zg_orb_features_per_level(C.byref(p), out))
+        return [int(v) for v in out[: self.n_levels]]
+
+    def adaptive_threshold(self, level: int) -> int:
+        """Orb.computeAdaptiveThreshold (:511-517)."""
+        p = self._params()
+        rc = L.lib().zg_orb_adaptive_threshold(C.byref(p), int(level))
+        if rc < 0:
+            L.check(-rc)
+        return rc
+
+    @staticmethod
+    def _image(image) -> "Image":
+        return image if isinstance(image, Image) else Image(image)
+
+    def detect_and_compute_into(self, image, keypoints, descriptors, count, capacity: Optional[int] = None) -> None:
+        """Asynchronous device form: zg_orb_detect_and_compute on the current stream into `keypoints` (a device tensor of at least
+        capacity x 28 bytes), `descriptors` (capacity x 32 bytes, or None for Orb.detect) and `count` (at least 4 bytes, receives
+        the full length as a u32). Nothing is synchronised."""
+        img = self._image(image)
+        if not img.on_device or not _is_torch(keypoints) or not _is_torch(count) or not (descriptors is None or _is_torch(descriptors)):
+            raise ValueError("detect_and_compute_into takes a device image and device tensors")
+        nbytes = keypoints.numel() * keypoints.element_size()
+        cap = nbytes // KEYPOINT_DTYPE.itemsize if capacity is None else int(capacity)
+        if cap * KEYPOINT_DTYPE.itemsize > nbytes or count.numel() * count.element_size() < 4:
+            raise ValueError("keypoints or count tensor too small")
+        if descriptors is not None and cap * 32 > descriptors.numel() * descriptors.element_size():
+            raise ValueError("descriptors tensor too small")
+        s, p = img._desc(), self._params()
+        with torch.cuda.device(img.data.device):
+            L.check(L.lib().zg_orb_detect_and_compute(C.byref(s), C.byref(p), C.c_void_p(keypoints.data_ptr()),
+                                                      C.c_void_p(descriptors.data_ptr()) if descriptors is not None else None, cap,
+                                                      C.c_void_p(count.data_ptr()), img._stream()))
+
+    def _run(self, image, with_descriptors: bool):
+        img = self._image(image)
+        cap = self.n_features  # the list is never longer
+        if not img.on_device:
+            kps = np.empty(cap, KEYPOINT_DTYPE)
+            des = np.empty(cap, BINARY_DESCRIPTOR_DTYPE)
+            count = C.c_uint32()
+            s, p = img._desc(), self._params()
+            L.check(L.lib().zg_orb_detect_and_compute_host(C.byref(s), C.byref(p), kps.ctypes.data if cap else None,
+                                                           des.ctypes.data if cap and with_descriptors else None, cap, C.byref(count)))
+            return kps[: count.value].copy(), des[: count.value].copy()
+        dev = img.data.device
+        kps = torch.empty(max(cap, 1) * KEYPOINT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        des = torch.empty(max(cap, 1) * 32, dtype=torch.uint8, device=dev) if with_descriptors else None
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.detect_and_compute_into(img, kps, des, count, cap)
+        n = int(count.item())
+        k = kps[: n * KEYPOINT_DTYPE.itemsize].cpu().numpy().view(KEYPOINT_DTYPE).copy()
+        d = des[: n * 32].cpu().numpy().view(BINARY_DESCRIPTOR_DTYPE).copy() if with_descriptors else None
+        return k, d
+
+    def detect(self, image) -> np.ndarray:
+        """Orb.detect (:119-130): host images through zg_orb_detect_and_compute_host, device images through
+        zg_orb_detect_and_compute on the current stream (synchronised to read the count)."""
+        return self._run(image, False)[0]
+
+    def detect_and_compute(self, image) -> Tuple[np.ndarray, np.ndarray]:
+        """Orb.detectAndCompute (:250-276): (keypoints, descriptors)."""
+        return self._run(image, True)
+
+    def compute(self, image, keypoints) -> np.ndarray:
+        """Orb.compute (:133-144): the descriptors of the caller's keypoints (a KEYPOINT_DTYPE array)."""
+        img = self._image(image)
+        kps = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE)
+        n = len(kps)
+        out = np.zeros(n, BINARY_DESCRIPTOR_DTYPE)
+        s, p = img._desc(), self._params()
+        if not img.on_device:
+            L.check(L.lib().zg_orb_compute_host(C.byref(s), C.byref(p), kps.ctypes.data if n else None, n, out.ctypes.data if n else None))
+            return out
+        dev = img.data.device
+        dk = torch.from_numpy(kps.view(np.uint8).reshape(-1).copy() if n else np.zeros(1, np.uint8)).to(dev)
+        dd = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().zg_orb_compute(C.byref(s), C.byref(p), C.c_void_p(dk.data_ptr()), n, C.c_void_p(dd.data_ptr()), img._stream()))
+        return dd[: n * 32].cpu().numpy().view(BINARY_DESCRIPTOR_DTYPE).copy()
+
+
 class ProjectiveTransform:
     """reference src/geometry/transforms.zig:197-231 (f32 matrix, project = M [x y 1]^T scaled by 1/w)."""
     kind = L.TRANSFORM_PROJECTIVE
