@@ -726,4 +726,8 @@ ZG_API void zg_jpeg_free(void *p);
  * (zignal_amd/_lib.py: _ORB_SIGNATURES) and Zig file (zig/zignal_hip_orb.zig). */
 #include "zignal_hip_orb.h"
 
+/* BruteForceMatcher (src/features/matcher.zig) on ORB's descriptors: a module of its own in the same way (_MATCH_SIGNATURES,
+ * zig/zignal_hip_match.zig). */
+#include "zignal_hip_match.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -5,11 +5,13 @@
 //! This program is the other half of that sentence: run it once with the toolchain the reference pins
 //! (build.zig.zon: minimum_zig_version 0.17.0-dev.1441+d5181a9c9) and the pytest beside it turns "unpinned" into "pinned":
 //!
-//!     zig run -O ReleaseFast tools/zig_golden.zig > tests/golden/zig_golden.json
+//!     zig run -O ReleaseFast --dep zignal -Mroot=tools/zig_golden.zig -Mzignal=<zignal checkout>/src/root.zig > tests/golden/zig_golden.json
 //!     python -m pytest tests/test_zig_golden.py -q          # skipped while the file is absent
 //!
+//! (The zignal module is what the `matcher` section calls; every other section is std only.)
+//!
 //! (ReleaseFast is what the reference's own CI and examples build with; Debug must give the same bits — none of this is fast-math.)
-//! Std only: every expression below is the reference's own, restated with its file:line, so the numbers are those zignal computes
+//! Std only but for the matcher section: every expression below is the reference's own, restated with its file:line, so the numbers are those zignal computes
 //! with this compiler — the same @exp, @sin, @cos, std.math.pow and std.math.cbrt calls on the same operands in the same order.
 //! Every f32 travels as the u32 of its bit pattern; sweeps carry their inputs, so the checker never has to re-derive them.
 //!
@@ -22,9 +24,13 @@
 //!   oklab_17 / lab_17       Rgb(u8) on the 17^3 lattice {0, 16, ..., 240, 255}^3 -> Oklab(f32) / Lab(f32)   src/color.zig:1261-1272, 1289-1310, 1381-1400
 //!   orb                     ORB's orientation weight table at comptime (961), atan2 in degrees on a sweep [y, x, degrees], cos / sin of
 //!                           degrees on a sweep [degrees, cos, sin]             src/features/orb.zig:340-357, 424-425, 432-433
+//!   matcher                 BruteForceMatcher.match / knnMatch / radiusMatch of the zignal module itself on clustered descriptors with
+//!                           tied distances; each case carries its inputs [query bytes, train bytes] and parameters. Pins what a
+//!                           restatement cannot: that std.mem.sort keeps equal distances in train order   src/features/matcher.zig:44-212
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
+const zignal = @import("zignal"); // the matcher section alone
 
 fn bits(x: f32) u32 {
     return @bitCast(x);
@@ -200,6 +206,109 @@ const orb_weights: [31 * 31]f32 = blk: {
     break :blk vals;
 };
 
+// ---- matcher: the reference's own BruteForceMatcher on inputs made here --------------------------------------------------------
+fn flipBits(d: *zignal.BinaryDescriptor, rng: *Lcg, n: u32) void {
+    for (0..n) |_| {
+        const b = rng.next() >> 24; // a bit may be hit twice: the distances that result are what the section records
+        d.bits[b / 8] ^= @as(u8, 1) << @as(u3, @intCast(b % 8));
+    }
+}
+
+/// Random train descriptors, a tenth of them copies or near copies of an earlier one; queries that are train entries with
+/// 0 .. 90 bits flipped, or random, a tenth of them copies of an earlier query: ties at every distance the tests look at.
+fn clusteredDescriptors(rng: *Lcg, query: []zignal.BinaryDescriptor, train: []zignal.BinaryDescriptor) void {
+    const flips = [_]u32{ 0, 3, 10, 30, 60, 64, 65, 90 };
+    for (train, 0..) |*t, i| {
+        for (&t.bits) |*b| b.* = @intCast(rng.next() >> 24);
+        if (i > 0 and rng.next() % 10 == 0) {
+            t.* = train[rng.next() % i];
+            if (rng.next() % 2 == 1) flipBits(t, rng, rng.next() % 39 + 1);
+        }
+    }
+    for (query, 0..) |*q, i| {
+        for (&q.bits) |*b| b.* = @intCast(rng.next() >> 24);
+        if (rng.next() % 5 != 0) {
+            q.* = train[rng.next() % train.len];
+            flipBits(q, rng, flips[rng.next() % flips.len]);
+        }
+        if (i > 0 and rng.next() % 10 == 0) q.* = query[rng.next() % i];
+    }
+}
+
+fn printDescriptors(w: anytype, ds: []const zignal.BinaryDescriptor) !void {
+    try w.print("[", .{});
+    for (ds, 0..) |d, i| {
+        for (d.bits, 0..) |b, j| try w.print("{s}{d}", .{ if (i == 0 and j == 0) "" else ",", b });
+    }
+    try w.print("]", .{});
+}
+
+fn printMatches(w: anytype, ms: anytype) !void {
+    try w.print("[", .{});
+    for (ms, 0..) |m, i| try w.print("{s}[{d},{d},{d}]", .{ if (i == 0) "" else ",", m.query_idx, m.train_idx, bits(m.distance) });
+    try w.print("]", .{});
+}
+
+fn printRows(w: anytype, allocator: std.mem.Allocator, rows: anytype) !void {
+    try w.print("[", .{});
+    for (rows, 0..) |row, i| {
+        if (i != 0) try w.print(",", .{});
+        try printMatches(w, row);
+        allocator.free(row);
+    }
+    allocator.free(rows);
+    try w.print("]", .{});
+}
+
+fn matcherSection(w: anytype, allocator: std.mem.Allocator) !void {
+    const shapes = [_][2]usize{ .{ 1, 1 }, .{ 5, 1 }, .{ 9, 40 }, .{ 65, 129 }, .{ 40, 300 } };
+    const ratios = [_]f32{ 0.8, 0.5, 1.0, 2.0, 0.0, std.math.inf(f32), std.math.nan(f32), -1.0 };
+    const max_distances = [_]u32{ 0, 64, 256, std.math.maxInt(u32) };
+    const radii = [_]f32{ -1.0, 0.0, 40.0, 64.5, 300.0, std.math.nan(f32) };
+    try w.print("  \"matcher\": [", .{});
+    for (shapes, 0..) |shape, si| {
+        var rng = Lcg{ .s = 40 + @as(u32, @intCast(si)) };
+        const query = try allocator.alloc(zignal.BinaryDescriptor, shape[0]);
+        defer allocator.free(query);
+        const train = try allocator.alloc(zignal.BinaryDescriptor, shape[1]);
+        defer allocator.free(train);
+        clusteredDescriptors(&rng, query, train);
+        try w.print("{s}\n   {{\"nq\": {d}, \"nt\": {d}, \"query\": ", .{ if (si == 0) "" else ",", shape[0], shape[1] });
+        try printDescriptors(w, query);
+        try w.print(", \"train\": ", .{});
+        try printDescriptors(w, train);
+        try w.print(", \"match\": [", .{});
+        var first = true;
+        for ([_]bool{ false, true }) |cross| for (max_distances) |md| for (ratios) |ratio| {
+            const m = zignal.BruteForceMatcher{ .cross_check = cross, .max_distance = md, .ratio_threshold = runtime(ratio) };
+            const got = try m.match(allocator, query, train);
+            defer allocator.free(got);
+            try w.print("{s}{{\"cross_check\": {d}, \"max_distance\": {d}, \"ratio_bits\": {d}, \"matches\": ", .{ if (first) "" else ",", @intFromBool(cross), md, bits(ratio) });
+            try printMatches(w, got);
+            try w.print("}}", .{});
+            first = false;
+        };
+        try w.print("], \"knn\": [", .{});
+        first = true;
+        for ([_]usize{ 1, 2, 3, shape[1], shape[1] + 5 }) |k| for (max_distances) |md| {
+            const m = zignal.BruteForceMatcher{ .max_distance = md };
+            try w.print("{s}{{\"k\": {d}, \"max_distance\": {d}, \"rows\": ", .{ if (first) "" else ",", k, md });
+            try printRows(w, allocator, try m.knnMatch(allocator, query, train, k));
+            try w.print("}}", .{});
+            first = false;
+        };
+        try w.print("], \"radius\": [", .{});
+        for (radii, 0..) |r, ri| {
+            const m = zignal.BruteForceMatcher{};
+            try w.print("{s}{{\"max_dist_bits\": {d}, \"rows\": ", .{ if (ri == 0) "" else ",", bits(r) });
+            try printRows(w, allocator, try m.radiusMatch(allocator, query, train, runtime(r)));
+            try w.print("}}", .{});
+        }
+        try w.print("]}}", .{});
+    }
+    try w.print("\n  ],\n", .{});
+}
+
 pub fn main(init: std.process.Init) !void {
     var buffer: [1 << 16]u8 = undefined;
     var stdout = std.Io.File.stdout().writer(init.io, &buffer);
@@ -287,6 +396,9 @@ pub fn main(init: std.process.Init) !void {
     try sweep(w, "pow24", fPow24, 15, 0.0404, 1.0, 4096, false);
     try sweep(w, "pow_third", fPowThird, 16, 0.008856, 1.1, 4096, false);
     try sweep(w, "pow_inv24", fPowInv24, 17, 0.0031308, 1.0, 4096, false);
+
+    // src/features/matcher.zig:44-212 through the zignal module
+    try matcherSection(w, init.gpa);
 
     // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
     // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])

@@ -102,6 +102,26 @@ class ZgOrbParams(C.Structure):
 ORB_HARRIS_SCORE, ORB_FAST_SCORE = range(2)
 
 
+class ZgMatch(C.Structure):
+    """zg_match == Match (src/features/matcher.zig:10-19) with 32-bit indices."""
+    _fields_ = [("query_idx", C.c_uint32), ("train_idx", C.c_uint32), ("distance", C.c_float)]
+
+
+class ZgDescriptorSet(C.Structure):
+    """zg_descriptor_set: a descriptor array, its capacity and the optional word that holds how many of them count."""
+    _fields_ = [("data", C.c_void_p), ("capacity", C.c_uint32), ("count", C.c_void_p)]
+
+
+class ZgMatcherParams(C.Structure):
+    """zg_matcher_params == BruteForceMatcher's fields (matcher.zig:33-41)."""
+    _fields_ = [("cross_check", C.c_int32), ("max_distance", C.c_uint32), ("ratio_threshold", C.c_float)]
+
+
+class ZgMatchStatistics(C.Structure):
+    """zg_match_statistics == MatchStats (matcher.zig:237-241)."""
+    _fields_ = [("total_matches", C.c_size_t), ("mean_distance", C.c_float), ("min_distance", C.c_float), ("max_distance", C.c_float)]
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -302,6 +322,23 @@ _ORB_RESTYPES = {"zg_orb_default_params": None}
 ORB_EXPORTED_SYMBOLS = tuple(_ORB_SIGNATURES)
 
 
+# the matcher module: every symbol include/zignal_hip_match.h declares
+_SET = C.POINTER(ZgDescriptorSet)
+_MATCH_SIGNATURES = {
+    "zg_matcher_default_params": [C.POINTER(ZgMatcherParams)],
+    "zg_match_train_chunk": [],
+    "zg_match_descriptors": [_SET, _SET, C.POINTER(ZgMatcherParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_match_knn": [_SET, _SET, C.POINTER(ZgMatcherParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_match_radius": [_SET, _SET, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_match_descriptors_host": [_SET, _SET, C.POINTER(ZgMatcherParams), C.c_void_p, C.c_uint32, _U32P],
+    "zg_match_knn_host": [_SET, _SET, C.POINTER(ZgMatcherParams), C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_match_radius_host": [_SET, _SET, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, _U32P],
+    "zg_match_stats": [C.c_void_p, C.c_size_t, C.POINTER(ZgMatchStatistics)],
+}
+_MATCH_RESTYPES = {"zg_matcher_default_params": None, "zg_match_train_chunk": C.c_uint32}
+MATCH_EXPORTED_SYMBOLS = tuple(_MATCH_SIGNATURES)
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -310,7 +347,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES)):
+        for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

@@ -655,4 +655,96 @@ struct Orb {
     }
 };
 
+// ---- features: BruteForceMatcher (src/features/matcher.zig) ----
+using Match = zg_match; // matcher.zig:10-19 with 32-bit indices
+static_assert(sizeof(Match) == 12, "zg_match is 12 bytes");
+
+// MatchStats (matcher.zig:237-270)
+struct MatchStats {
+    size_t total_matches = 0;
+    float mean_distance = 0, min_distance = 0, max_distance = 0;
+    static MatchStats compute(const std::vector<Match> &matches) {
+        zg_match_statistics s{};
+        check(zg_match_stats(matches.empty() ? nullptr : matches.data(), matches.size(), &s));
+        MatchStats out;
+        out.total_matches = s.total_matches;
+        out.mean_distance = s.mean_distance;
+        out.min_distance = s.min_distance;
+        out.max_distance = s.max_distance;
+        return out;
+    }
+};
+
+// BruteForceMatcher (matcher.zig:33-41): the reference's fields and defaults; match / knnMatch / radiusMatch return its lists, order
+// included, bit for bit.
+struct BruteForceMatcher {
+    bool cross_check = false;
+    uint32_t max_distance = 64;
+    float ratio_threshold = 0.8f;
+
+    // a descriptor array in device memory and, optionally, the device word that says how many count (what Orb::detectAndComputeInto wrote)
+    struct DeviceDescriptors {
+        const BinaryDescriptor *data;
+        uint32_t capacity;
+        const uint32_t *count = nullptr;
+        zg_descriptor_set set() const { return zg_descriptor_set{data, capacity, count}; }
+    };
+
+    zg_matcher_params params() const { return zg_matcher_params{cross_check ? 1 : 0, max_distance, ratio_threshold}; }
+    static zg_descriptor_set hostSet(const std::vector<BinaryDescriptor> &d) {
+        return zg_descriptor_set{d.empty() ? nullptr : d.data(), (uint32_t)d.size(), nullptr};
+    }
+
+    std::vector<Match> match(const std::vector<BinaryDescriptor> &query, const std::vector<BinaryDescriptor> &train) const { // :44-106
+        const zg_descriptor_set q = hostSet(query), t = hostSet(train);
+        const zg_matcher_params p = params();
+        std::vector<Match> out(query.size());
+        uint32_t n = 0;
+        check(zg_match_descriptors_host(&q, &t, &p, out.empty() ? nullptr : out.data(), q.capacity, &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<std::vector<Match>> knnMatch(const std::vector<BinaryDescriptor> &query, const std::vector<BinaryDescriptor> &train, size_t k) const { // :109-162
+        if (query.empty() || train.empty() || k == 0) return {};
+        const zg_descriptor_set q = hostSet(query), t = hostSet(train);
+        const zg_matcher_params p = params();
+        const uint32_t kk = (uint32_t)(k < train.size() ? k : train.size()); // a row is never longer
+        std::vector<Match> flat(query.size() * kk);
+        std::vector<uint32_t> rows(query.size());
+        check(zg_match_knn_host(&q, &t, &p, kk, flat.data(), rows.data()));
+        std::vector<std::vector<Match>> out(query.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i].assign(flat.begin() + i * kk, flat.begin() + i * kk + rows[i]);
+        return out;
+    }
+    std::vector<std::vector<Match>> radiusMatch(const std::vector<BinaryDescriptor> &query, const std::vector<BinaryDescriptor> &train, float max_dist) const { // :165-212
+        if (query.empty() || train.empty()) return {};
+        const zg_descriptor_set q = hostSet(query), t = hostSet(train);
+        std::vector<uint32_t> rows(query.size());
+        uint32_t n = 0;
+        check(zg_match_radius_host(&q, &t, max_dist, nullptr, 0, rows.data(), &n)); // the row lengths first
+        std::vector<Match> flat(n);
+        if (n) check(zg_match_radius_host(&q, &t, max_dist, flat.data(), n, rows.data(), &n));
+        std::vector<std::vector<Match>> out(query.size());
+        size_t at = 0;
+        for (size_t i = 0; i < out.size(); at += rows[i++]) out[i].assign(flat.begin() + at, flat.begin() + at + rows[i]);
+        return out;
+    }
+    // asynchronous device forms: every pointer is device memory; nothing is synchronised, all three can be recorded into a graph
+    void matchInto(const DeviceDescriptors &query, const DeviceDescriptors &train, Match *matches, uint32_t capacity, uint32_t *count, zg_stream stream = nullptr) const {
+        const zg_descriptor_set q = query.set(), t = train.set();
+        const zg_matcher_params p = params();
+        check(zg_match_descriptors(&q, &t, &p, matches, capacity, count, stream));
+    }
+    void knnMatchInto(const DeviceDescriptors &query, const DeviceDescriptors &train, uint32_t k, Match *matches, uint32_t *row_counts, zg_stream stream = nullptr) const {
+        const zg_descriptor_set q = query.set(), t = train.set();
+        const zg_matcher_params p = params();
+        check(zg_match_knn(&q, &t, &p, k, matches, row_counts, stream));
+    }
+    void radiusMatchInto(const DeviceDescriptors &query, const DeviceDescriptors &train, float max_dist, Match *matches, uint32_t capacity, uint32_t *row_counts,
+                         uint32_t *count, zg_stream stream = nullptr) const {
+        const zg_descriptor_set q = query.set(), t = train.set();
+        check(zg_match_radius(&q, &t, max_dist, matches, capacity, row_counts, count, stream));
+    }
+};
+
 } // namespace zignal
