@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 import zignal_amd as zg
 from tests.util import assert_bits_equal, synth
@@ -52,3 +53,34 @@ def test_banded_views_and_convert(oracle, small_bands):
     same = plain.copy()
     zg.Image(same).gaussian_blur(0.6, out=zg.Image(same))
     assert_bits_equal(same, oracle.gaussian_blur(plain, 0.6), "in place")
+
+
+# ---- the whole-frame path of the host-pointer entry points no other test calls ---------------------------------------------
+# (zg_common.h: host_src_dst / host_in_place). Each op takes an Image and returns the Image that holds its result.
+_I = zg.Interpolation
+WHOLE_FRAME_OPS = {
+    "warp": ("rgba_f32", lambda s: s.warp(zg.AffineTransform([[0.9, 0.2], [-0.2, 0.9]], [3.0, -2.0]), (33, 49), _I.bilinear)),
+    "rotate_into": ("rgb_u8", lambda s: s.rotate(0.3, _I.bilinear, zg.BorderMode.mirror)),
+    "extract": ("f32", lambda s: s.extract((5.0, 4.0, 40.0, 30.0), 0.4, (21, 27), _I.catmull_rom, zg.BorderMode.replicate)),
+    "motion_blur_radial": ("rgb_f32", lambda s: s.motion_blur_radial(0.4, 0.55, 0.5, False)),
+    "flip_top_bottom": ("f32", lambda s: s.flip_top_bottom()),
+    "fill": ("rgb_u8", lambda s: s.fill((7, 8, 9))),
+}
+
+
+@pytest.mark.parametrize("name", sorted(WHOLE_FRAME_OPS))
+def test_whole_frame_host_call_equals_the_stream_call(oracle, name):
+    """zg_<name>_host on a 37 x 53 numpy image, and on a 37 x 53 view of a 45 x 64 one, against zg_<name> on the same pixels in
+    device memory, byte for byte. The shape is off every 16- and 64-pixel grid and far too small for host_banded."""
+    kind, op = WHOLE_FRAME_OPS[name]
+    big = synth(oracle, kind, 92, 45, 64)
+    small = np.ascontiguousarray(big[4:41, 7:60])
+    want = op(zg.Image(torch.from_numpy(small.copy()).cuda())).to_numpy()
+    assert_bits_equal(op(zg.Image(small.copy())).data, want, f"{name}: contiguous host image")
+    held = big.copy()
+    assert_bits_equal(op(zg.Image(held).view((7, 4, 60, 41))).data, want, f"{name}: host view, stride 64")
+    # the in-place ops (fill, the flip) write the view back: the pixels around it must come through untouched.
+    # For the others `held` is only a source, and this says that a source is never written.
+    outside = np.ones(big.shape[:2], bool)
+    outside[4:41, 7:60] = False
+    assert np.array_equal(held[outside], big[outside]), f"{name}: pixels outside the view changed"

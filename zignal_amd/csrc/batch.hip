@@ -7,7 +7,7 @@
 //     bilinear fused (conv_sep_rgba8.hip); per frame the HBM traffic is the source read once + the small output.
 //   * Rgba(u8) otherwise: one batched blur launch into scratch frames, then resize per frame.
 //   * anything else: gaussianBlur + resize per frame.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -15,18 +15,6 @@
 #include <vector>
 
 namespace zg {
-int resize_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s);
-struct Rgba8Batch {
-    const void *src; void *dst;
-    uint32_t n_frames, rows, cols;
-    size_t src_stride, dst_stride, src_frame_px, dst_frame_px;
-    bool down2;
-};
-int try_sep_rgba8_batch(const Rgba8Batch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
-}
-
-namespace zg {
-int convert_impl(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const float *srgb_lut, hipStream_t s);
 
 namespace {
 

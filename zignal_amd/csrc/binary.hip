@@ -7,12 +7,9 @@
 //   dilate/erode/open/close  structuring element in the kernel arguments (<= 15 x 15, non-zero = on, centre anchor, not
 //                          flipped); dilation ignores out-of-image samples, erosion treats them as background
 //                          (binary.zig:121-281). Iterations ping-pong between scratch planes.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
-int sat_planes_impl(const zg_image *src, float *sat, hipStream_t s, bool integer_valued, size_t plane_stride = 0); // box_blur.hip (0: planes contiguous)
 
 __global__ __launch_bounds__(256) void k_hist_u8(DImg src, unsigned int *hist) {
     __shared__ unsigned int lh[16][256];
@@ -206,38 +203,20 @@ extern "C" {
 
 int zg_threshold_otsu(const zg_image *src, const zg_image *dst, uint8_t *threshold_out, zg_stream stream) { return otsu_impl(src, dst, threshold_out, as_stream(stream)); }
 int zg_threshold_otsu_host(const zg_image *src, const zg_image *dst, uint8_t *threshold_out) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = otsu_impl(&a.dev, &b.dev, threshold_out, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return otsu_impl(a, b, threshold_out, nullptr); });
 }
 int zg_threshold_adaptive_mean(const zg_image *src, const zg_image *dst, uint32_t radius, float c, zg_stream stream) {
     return adaptive_impl(src, dst, radius, c, as_stream(stream));
 }
 int zg_threshold_adaptive_mean_host(const zg_image *src, const zg_image *dst, uint32_t radius, float c) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = adaptive_impl(&a.dev, &b.dev, radius, c, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return adaptive_impl(a, b, radius, c, nullptr); });
 }
 int zg_morph(const zg_image *src, const zg_image *dst, const uint8_t *kernel, uint32_t kernel_rows, uint32_t kernel_cols, uint32_t iterations, int op,
              zg_stream stream) {
     return morph_impl(src, dst, kernel, kernel_rows, kernel_cols, iterations, op, as_stream(stream));
 }
 int zg_morph_host(const zg_image *src, const zg_image *dst, const uint8_t *kernel, uint32_t kernel_rows, uint32_t kernel_cols, uint32_t iterations, int op) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = morph_impl(&a.dev, &b.dev, kernel, kernel_rows, kernel_cols, iterations, op, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return morph_impl(a, b, kernel, kernel_rows, kernel_cols, iterations, op, nullptr); });
 }
 
 } // extern "C"

@@ -19,7 +19,7 @@
 //                    once: a chain wave alone on its SIMD, eight loader waves, four storer waves per 64 columns of one channel
 // then, for both:
 //   k_box_mean   one thread per pixel: four SAT taps (buffer loads), divide by the clipped area, clamp.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -27,9 +27,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
-int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, bool sharpen, hipStream_t s); // box_fused.hip
 
 // Row pass. The running sum along a row is a sequential f32 chain (f32 addition is not associative and the reference's
 // rounding must be reproduced), so the parallelism is rows x channels. One wave owns 64 rows of one channel: per chunk
@@ -656,8 +653,7 @@ int sat_planes_impl(const zg_image *src, float *sat, hipStream_t s, bool integer
 // Integral images of up to three single-channel planes (u8 or integer-valued f32) of one size, one launch pair for all of them.
 int sat_planes_multi(const zg_image *const *srcs, float *const *sats, int count, hipStream_t s) {
     const zg_image *a = srcs[0];
-    static const bool fused_off = getenv("ZIGNAL_HIP_SAT_UNFUSED") != nullptr;
-    bool ok = count >= 1 && count <= 3 && a->cols <= 65536 && !fused_off;
+    bool ok = count >= 1 && count <= 3 && sat_fused_applies(a, true); // every plane here is integer-valued
     for (int i = 0; i < count && ok; ++i)
         ok = srcs[i]->rows == a->rows && srcs[i]->cols == a->cols && (srcs[i]->pixel == ZG_PIXEL_U8 || srcs[i]->pixel == ZG_PIXEL_F32);
     if (!ok) { // one at a time
@@ -815,13 +811,7 @@ int zg_box_blur(const zg_image *src, const zg_image *dst, uint32_t radius, zg_st
 }
 
 int zg_box_blur_host(const zg_image *src, const zg_image *dst, uint32_t radius) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = box_blur_impl(&a.dev, &b.dev, radius, false, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return box_blur_impl(a, b, radius, false, nullptr); });
 }
 
 int zg_sharpen(const zg_image *src, const zg_image *dst, uint32_t radius, zg_stream stream) {
@@ -829,13 +819,7 @@ int zg_sharpen(const zg_image *src, const zg_image *dst, uint32_t radius, zg_str
 }
 
 int zg_sharpen_host(const zg_image *src, const zg_image *dst, uint32_t radius) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = box_blur_impl(&a.dev, &b.dev, radius, true, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return box_blur_impl(a, b, radius, true, nullptr); });
 }
 
 // Image(T).integral (image.zig:628-630 -> integral.zig:95-140): planes[ch] is a rows x cols f32 image, ch-major in `planes`.

@@ -32,7 +32,7 @@
 // integer n and area <= 49, so a v that is not exactly k + 1/2 is at least 1 / 98 away from it (2^-10 cannot carry it across, nor can the quotient's
 // rounding error of <= 2^-16), and k + 1/2 + 2^-10 is representable and rounds up, which is what half-away does for v >= 0; negative v saturate to 0
 // either way. The same holds for sharpen's 2 * original - v.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -41,8 +41,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
 
 constexpr int BF_W = 16;        // output pixel columns per strip: 4096 columns = 256 strips = one workgroup per CU
 constexpr int BF_NP = 2;        // row-prefix ring: block s - 1 is written (at the end of its loaders' second step) while block s - 2 is read

@@ -12,7 +12,7 @@
 //
 // The legacy fast path (Rgb / Rgba / grey sources to grey, Rgb, Rgba, Oklab, Xyz, u8 Ycbcr: k_convert in convert.hip,
 // with the 256-entry sRGB table) stays as it is; this kernel takes every other pair.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_devmath.h"
 
 #pragma clang fp contract(off)

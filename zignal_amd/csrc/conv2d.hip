@@ -5,7 +5,7 @@
 // accumulate, divClampU8(256). Out-of-range taps go through border.resolveIndex (the reference's interior fast
 // path computes the same sums). Struct pixels run per channel on interleaved data (the reference's split /
 // plane / merge, :213-293, gives the same bytes; its uniform-channel shortcut is value-preserving).
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -14,8 +14,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int try_conv2d_stream(const zg_image *src, const zg_image *dst, const float *taps, int kh, int kw, int border, hipStream_t s); // conv2d_stream.hip
 
 constexpr int MAX_K2D = 15 * 15;
 
@@ -50,9 +48,7 @@ __global__ __launch_bounds__(256) void k_conv2d(DImg src, DImg dst, Kernel2D k, 
     const int hh = kh / 2, hw = kw / 2;
     const int lw = C2_TW + kw - 1, lh = C2_TH + kh - 1;
 
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
     const int x0 = tx * C2_TW, y0 = ty * C2_TH;
 
@@ -286,13 +282,7 @@ int zg_convolve_host(const zg_image *src, const zg_image *dst, const float *kern
         const int brc = host_banded(src, dst, kh / 2, [&](const zg_image *sv, const zg_image *dv, hipStream_t s) { return convolve_impl(sv, dv, kernel, kh, kw, border, s); });
         if (brc >= 0) return brc;
     }
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = convolve_impl(&a.dev, &b.dev, kernel, kh, kw, border, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return convolve_impl(a, b, kernel, kh, kw, border, nullptr); });
 }
 
 } // extern "C"

@@ -17,7 +17,7 @@
 //
 // Preconditions (else k_conv2d runs): u8 / Rgb(u8) / Rgba(u8), square kernel of 3 or 5, 255 * sum|round(256 k)| < 2^24, row length and
 // pitches multiples of 16 bytes, 16-byte aligned bases, at least 64 pixels per row and 16 rows, spans below 4 GiB for the fast path.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 #include "zg_stream.h"
 
@@ -56,9 +56,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(C2S_WAVES)))
     constexpr int D = K * DM;            // source rows in flight ahead of the arithmetic = rows per unrolled block
     static_assert((H + 1) * SP <= 16, "the border halo must come out of the outer lane's own unit");
 
-    const uint32_t nwg = gridDim.x, per_xcd = nwg >> 3;
-    uint32_t w = blockIdx.x;
-    if (ZG_XCD_ORDER && w < (per_xcd << 3)) w = (w & 7) * per_xcd + (w >> 3); // XCD-major: an XCD's L2 sees whole bands of neighbouring strips
+    const uint32_t w = xcd_major((uint32_t)blockIdx.x, (uint32_t)gridDim.x); // XCD-major: an XCD's L2 sees whole bands of neighbouring strips
     const int sy = (int)(w / (uint32_t)a.strips_x), sx = (int)(w - (uint32_t)sy * (uint32_t)a.strips_x);
 
     const int lx = (int)threadIdx.x;

@@ -14,7 +14,7 @@
 // Tile = 1024 bytes x 4*RPT rows per workgroup, staged in LDS as 16-byte units with one halo unit on each side
 // (H*SP <= 12 bytes). Preconditions (else the general kernel runs): u8 or Rgb(u8), row length and strides multiples of
 // 16 bytes, 16-byte aligned bases, odd equal tap counts <= 9, taps as above.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 
 namespace zg {
@@ -127,9 +127,7 @@ __global__ __launch_bounds__(256) void k_sep_bytes(DImg src, DImg dst, TapsU8<NK
     constexpr int TH = 4 * RPT;
     __shared__ u32x4 tile[Stage::LH * R8_UNITS];
 
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3); // XCD-major order
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x); // XCD-major order
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
     const int xb0 = tx * 1024, y0 = ty * TH;
     const int lx = threadIdx.x & 63;

@@ -20,7 +20,7 @@
 //
 // Preconditions (else the general two-pass kernels run): u8 pixel types, row length and strides multiples of 16 bytes,
 // 16-byte aligned bases, row >= 256 bytes, taps as above, both tap counts <= 65.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 
 #include <cstdlib>
@@ -723,8 +723,6 @@ __global__ __launch_bounds__(256) void k_cols_bilinear_u8_multi(FusedJobs jobs) 
         else cols_bilinear_band<false, false>(a, job.taps, bt, tx, band);
     }
 }
-
-int resize_impl_bilinear_u8(const zg_image *src, const zg_image *dst, hipStream_t s); // edges.hip: zg_resize(.bilinear)
 
 // Levels i with handled[i] set on return were enqueued here (on `s`); the others are the caller's. A caller with several streams asks for the fused levels on
 // one and the dense levels on another (two independent batches, each with its own row-pass launch and scratch block: no event between the streams). sigmas[i] <= 0.5 (a plain resize), other pixel types,

@@ -15,7 +15,7 @@
 //                   accumulator receives its taps in ascending order, as the reference's inner loop does.
 // Preconditions (else the general kernels run): f32 pixel types, row length and strides multiples of 4 elements, 16-byte
 // aligned bases, row >= 256 elements, no negligible tap, both tap counts <= 65.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #pragma clang fp contract(off)
 

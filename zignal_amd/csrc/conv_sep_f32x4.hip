@@ -9,7 +9,7 @@
 //
 // Preconditions (else the general kernel runs): f32, cols % 4 == 0, strides % 4 == 0, 16-byte aligned bases,
 // cols >= 64, odd equal tap counts <= 9.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -83,9 +83,7 @@ __global__ __launch_bounds__(256) void k_sep_f32x4(DImg src, DImg dst, TapsF32<N
     constexpr int TH = 4 * RPT;
     __shared__ f32x4 tile[Stage::LH * F4_UNITS];
 
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3); // XCD-major tile order
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x); // XCD-major tile order
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
     const int x0 = tx * F4_TW, y0 = ty * TH;
     const int lx = threadIdx.x & 63;

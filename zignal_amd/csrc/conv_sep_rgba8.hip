@@ -12,7 +12,7 @@
 //
 // Preconditions (checked by the caller, else the general kernel runs): Rgba(u8), cols % 4 == 0, strides % 4 == 0,
 // 16-byte aligned bases, odd equal tap counts <= 9, taps as above.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 #include <algorithm>
 #include <cstdlib>
@@ -203,9 +203,7 @@ __global__ __launch_bounds__(256) void k_sep_rgba8(DImg src, DImg dst, size_t sr
     constexpr int TH = 4 * RPT;
     __shared__ u32x4 tile[Stage::LH * R8_UNITS];
 
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3); // XCD-major order
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x); // XCD-major order
     const int frame = wg / tiles_per_frame, t = wg - frame * tiles_per_frame;
     const int ty = t / tiles_x, tx = t - ty * tiles_x;
     src.data = (uint32_t *)src.data + (size_t)frame * src_frame_px;
@@ -223,14 +221,6 @@ __global__ __launch_bounds__(256) void k_sep_rgba8(DImg src, DImg dst, size_t sr
     __syncthreads();
     convolve_tile8<NK, RPT, NT, CLAMP, DOWN2>(tile, dst, kx, ky, tx * R8_TW, ty * TH, lx, wave);
 }
-
-struct Rgba8Batch { // frames laid out back to back
-    const void *src; void *dst;
-    uint32_t n_frames, rows, cols;
-    size_t src_stride, dst_stride;         // row strides in pixels
-    size_t src_frame_px, dst_frame_px;     // frame strides in pixels
-    bool down2;                            // dst is (rows/2) x (cols/2): blur then 2:1 bilinear
-};
 
 template <int NK, int RPT, bool CLAMP, bool DOWN2>
 static int launch_rgba8(const Rgba8Batch &b, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
@@ -271,12 +261,6 @@ int try_sep_rgba8_batch(const Rgba8Batch &b, const int32_t *ix, const int32_t *i
     switch (nk) { ZG_R8(3) ZG_R8(5) ZG_R8(7) ZG_R8(9) }
 #undef ZG_R8
     return -1;
-}
-
-int try_sep_rgba8(const zg_image *src, const zg_image *dst, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s) {
-    if (src->pixel != ZG_PIXEL_RGBA_U8) return -1;
-    Rgba8Batch b{src->data, dst->data, 1, src->rows, src->cols, src->stride, dst->stride, 0, 0, false};
-    return try_sep_rgba8_batch(b, ix, iy, nk, border, s);
 }
 
 } // namespace zg

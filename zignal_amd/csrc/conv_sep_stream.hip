@@ -26,7 +26,7 @@
 //
 // Preconditions (else the tiled kernels run): u8 / Rgb(u8) / Rgba(u8), row length and pitches multiples of 16 bytes,
 // 16-byte aligned bases, odd equal tap counts with (H + 1) * SP <= 16, taps as above, at least 64 pixels per row and 16 rows.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 #include "zg_stream.h"
 
@@ -131,9 +131,7 @@ __global__ __launch_bounds__(64) void k_sep_stream(StreamArgs a, TapsU8<NK> kx, 
 #ifdef ZG_STREAM_TRACE
     const unsigned long long trace_r0 = wall_clock64(), trace_c0 = clock64();
 #endif
-    const uint32_t nwg = gridDim.x, per_xcd = nwg >> 3;
-    uint32_t w = blockIdx.x;
-    if (ZG_XCD_ORDER && w < (per_xcd << 3)) w = (w & 7) * per_xcd + (w >> 3); // XCD-major: an XCD's L2 sees whole bands of neighbouring strips
+    const uint32_t w = xcd_major((uint32_t)blockIdx.x, (uint32_t)gridDim.x); // XCD-major: an XCD's L2 sees whole bands of neighbouring strips
     const uint32_t per_frame = (uint32_t)(a.strips_x * a.strips_y);
     const uint32_t frame = w / per_frame, t = w - frame * per_frame;
     const int sy = (int)(t / (uint32_t)a.strips_x), sx = (int)(t - (uint32_t)sy * (uint32_t)a.strips_x);

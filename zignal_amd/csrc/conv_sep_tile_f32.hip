@@ -25,7 +25,7 @@
 // Preconditions (else conv_sep_f32x4.hip / the general kernels run): f32 planes, cols % 4 == 0, strides % 4 == 0, 16-byte aligned
 // bases, cols >= 64, rows >= 16, odd equal tap counts 3 / 5 / 7, no tap below the reference's skip threshold (|k| < 1e-10 is
 // skipped for interior pixels only, convolution.zig:459-467 — the tiled kernel carries that mask).
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_stream.h"
 
 #include <algorithm>
@@ -36,8 +36,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-constexpr int SF_MAX_PLANES = 8;
 
 template <int N> struct TapsSF { float k[N]; };
 

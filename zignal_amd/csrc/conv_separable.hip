@@ -25,15 +25,13 @@
 //       the window, one coalesced store. HBM traffic = read once + write once.
 //   k_sep_h / k_sep_v              general two-pass fallback for long or asymmetric kernels
 //       (temp plane in HBM, as the reference does).
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_hostmath.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -83,12 +81,10 @@ constexpr int TW = 64;  // tile width = one wavefront of columns; tile height = 
 
 // Kernel shape parameters (measured on MI355X, profiles/r01_sep_variant_sweep.txt):
 //   RPT      output rows per thread (tile height = 4 * RPT); 4 for 16-byte pixels, 8 otherwise
-//   PERSIST  persistent workgroups that prefetch tile t+1 into registers while convolving tile t (measured slower; kept
-//            selectable for future geometries)
 //   NT       non-temporal stores for the output (always on; non-temporal LOADS measured slower)
 
-// Tile staging shared by the persistent kernel: load one (TH+2H) x (TW+2H) source tile into registers
-// (every load issued back to back), and later spill those registers to LDS.
+// Tile staging: load one (TH+2H) x (TW+2H) source tile into registers (every load issued back to back), and
+// later spill those registers to LDS.
 template <int PIX, int NK, int RPT> struct TileStage {
     using P = Px<PIX>;
     using Vec = typename P::Vec;
@@ -267,13 +263,11 @@ __device__ __forceinline__ void convolve_tile(const typename Px<PIX>::Vec *tile,
     }
 }
 
-// Persistent, software-pipelined fused kernel. Each workgroup owns a contiguous run of tiles; while it
-// convolves tile t out of LDS, the global loads of tile t+1 are already in flight into registers, so a CU
-// never drains its memory queue between tiles. grid = min(#tiles, resident workgroups).
-template <int PIX, int NK, int MODE, bool SKIP, int RPT, bool PERSIST, bool NT>
+// The fused kernel: one tile per workgroup; the hardware dispatcher overlaps the load and compute phases of the
+// workgroups that share a CU.
+template <int PIX, int NK, int MODE, bool SKIP, int RPT, bool NT>
 __global__ __launch_bounds__(256) void k_sep_fused(DImg src, DImg dst, TapsArg<NK> kx, TapsArg<NK> ky,
-                                                   int border, uint32_t skipx, uint32_t skipy, int tiles_x,
-                                                   int n_tiles) {
+                                                   int border, uint32_t skipx, uint32_t skipy, int tiles_x) {
     using P = Px<PIX>;
     using Vec = typename P::Vec;
     using Stage = TileStage<PIX, NK, RPT>;
@@ -288,42 +282,14 @@ __global__ __launch_bounds__(256) void k_sep_fused(DImg src, DImg dst, TapsArg<N
 
     // Workgroup b sits on XCD b % 8 (private L2 per XCD): number the workgroups XCD-major so that each XCD
     // sweeps one contiguous band of the image and neighbouring tiles (which share halo lines) hit the same L2.
-    const int nwg = gridDim.x;
-    const int per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
 
     Stage st;
-    if constexpr (!PERSIST) { // one tile per workgroup; the hardware dispatcher overlaps load and compute phases
-        const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
-        st.load(src, tx * TW, ty * TH, border, lx, wave);
-        st.spill(tile, lx, wave);
-        __syncthreads();
-        convolve_tile<PIX, NK, MODE, SKIP, RPT, NT>(tile, src, dst, kx, ky, skipx, skipy, tx * TW, ty * TH, lx, wave);
-    } else {
-        // Tiles [t_begin, t_end) of this workgroup; tile t+1 is prefetched into registers while tile t is convolved.
-        const int t_begin = (int)(((long long)n_tiles * wg) / nwg);
-        const int t_end = (int)(((long long)n_tiles * (wg + 1)) / nwg);
-        if (t_begin >= t_end) return;
-        int ty = t_begin / tiles_x, tx = t_begin - ty * tiles_x;
-        st.load(src, tx * TW, ty * TH, border, lx, wave);
-        st.spill(tile, lx, wave);
-        __syncthreads();
-        // Steady state, straight-line per iteration: [loads of t+1] [convolve t: LDS reads, NK-row window, stores]
-        // [barrier] [spill t+1 -> LDS] [barrier]. The spill waits on the loads only (vmcnt = #stores behind them).
-        for (int t = t_begin; t + 1 < t_end; ++t) {
-            int ny = ty, nx = tx + 1;
-            if (nx == tiles_x) { nx = 0; ++ny; }
-            st.load(src, nx * TW, ny * TH, border, lx, wave);
-            convolve_tile<PIX, NK, MODE, SKIP, RPT, NT>(tile, src, dst, kx, ky, skipx, skipy, tx * TW, ty * TH, lx, wave);
-            __syncthreads(); // every wave is done reading tile t
-            st.spill(tile, lx, wave);
-            __syncthreads();
-            tx = nx;
-            ty = ny;
-        }
-        convolve_tile<PIX, NK, MODE, SKIP, RPT, NT>(tile, src, dst, kx, ky, skipx, skipy, tx * TW, ty * TH, lx, wave);
-    }
+    const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
+    st.load(src, tx * TW, ty * TH, border, lx, wave);
+    st.spill(tile, lx, wave);
+    __syncthreads();
+    convolve_tile<PIX, NK, MODE, SKIP, RPT, NT>(tile, src, dst, kx, ky, skipx, skipy, tx * TW, ty * TH, lx, wave);
 }
 
 // ---- general two-pass fallback ----------------------------------------------------------------
@@ -417,6 +383,14 @@ __global__ __launch_bounds__(256) void k_sep_v(const typename Arith<MODE>::Temp 
 }
 
 // ---- host dispatch ----------------------------------------------------------------------------
+// Bit i set: f32 tap i is one that interior pixels skip (|k| < 1e-10, convolution.zig:459-467). The fused kernels carry 32 bits of it.
+static uint32_t skip_mask(const float *k, uint32_t nk) {
+    uint32_t mask = 0;
+    for (uint32_t i = 0; i < nk && i < 32; ++i)
+        if (std::fabs(k[i]) < 1e-10f) mask |= 1u << i;
+    return mask;
+}
+
 struct SepPlan {
     int nkx, nky;
     std::vector<float> fx, fy;
@@ -425,23 +399,7 @@ struct SepPlan {
     int mode = MODE_F32;
 };
 
-// Workgroups that are resident at once for `kernel` (256 threads, static LDS): CUs x blocks per CU, cached.
-static int persistent_grid(const void *kernel) {
-    static std::mutex mu;
-    static std::unordered_map<const void *, int> cache;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(kernel);
-    if (it != cache.end()) return it->second;
-    int dev = 0, cus = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int grid = cus * std::min(per_cu, 8);
-    cache[kernel] = grid;
-    return grid;
-}
-
-template <int PIX, int NK, int MODE, bool SKIP, int RPT, bool PERSIST, bool NT>
+template <int PIX, int NK, int MODE, bool SKIP, int RPT, bool NT>
 static int launch_fused_v(const zg_image *src, const zg_image *dst, const SepPlan &p, int border, hipStream_t s) {
     TapsArg<NK> kx, ky;
     for (int i = 0; i < NK; ++i) {
@@ -449,11 +407,8 @@ static int launch_fused_v(const zg_image *src, const zg_image *dst, const SepPla
         else { kx.i[i] = p.ix[i]; ky.i[i] = p.iy[i]; }
     }
     const int tiles_x = (int)ceil_div(src->cols, TW), tiles_y = (int)ceil_div(src->rows, 4 * RPT);
-    const int n_tiles = tiles_x * tiles_y;
-    auto kernel = k_sep_fused<PIX, NK, MODE, SKIP, RPT, PERSIST, NT>;
-    const int grid = PERSIST ? std::min(n_tiles, persistent_grid((const void *)kernel)) : n_tiles;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, s,
-                       dimg(src), dimg(dst), kx, ky, border, p.skipx, p.skipy, tiles_x, n_tiles);
+    hipLaunchKernelGGL((k_sep_fused<PIX, NK, MODE, SKIP, RPT, NT>), dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s,
+                       dimg(src), dimg(dst), kx, ky, border, p.skipx, p.skipy, tiles_x);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
@@ -462,8 +417,8 @@ template <int PIX, int NK, int MODE, bool SKIP>
 static int launch_fused(const zg_image *src, const zg_image *dst, const SepPlan &p, int border, hipStream_t s) {
     // measured on MI355X (profiles/r01_sep_variant_sweep.txt): 16-byte pixels like many small tiles (more
     // workgroups per CU overlap each other's load and compute phases); every type likes streaming stores.
-    if constexpr (Px<PIX>::BYTES >= 12) return launch_fused_v<PIX, NK, MODE, SKIP, 4, false, true>(src, dst, p, border, s);
-    else return launch_fused_v<PIX, NK, MODE, SKIP, 8, false, true>(src, dst, p, border, s);
+    if constexpr (Px<PIX>::BYTES >= 12) return launch_fused_v<PIX, NK, MODE, SKIP, 4, true>(src, dst, p, border, s);
+    else return launch_fused_v<PIX, NK, MODE, SKIP, 8, true>(src, dst, p, border, s);
 }
 
 template <int PIX, int NK, int MODE>
@@ -542,16 +497,6 @@ static int run_sep(const zg_image *src, const zg_image *dst, const SepPlan &p, i
     return launch_two_pass<PIX, MODE>(src, dst, p, border, s);
 }
 
-int try_sep_rgba8(const zg_image *src, const zg_image *dst, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
-int try_sep_bytes(const zg_image *src, const zg_image *dst, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
-int try_sep_f32long(const zg_image *src, const zg_image *dst, const float *fx, int nkx, const float *fy, int nky, int border, hipStream_t s);
-int try_sep_bytes2(const zg_image *src, const zg_image *dst, const int32_t *ix, int nkx, const int32_t *iy, int nky, int border, hipStream_t s);
-int try_sep_f32x4(const zg_image *src, const zg_image *dst, const float *fx, const float *fy, int nk, uint32_t skipx, uint32_t skipy,
-                  int border, hipStream_t s);
-constexpr uint32_t SF_MAX_PLANES = 8; // planes per launch of conv_sep_tile_f32.hip
-int try_sep_tile_f32(const zg_image *src, const zg_image *dst, uint32_t n, const float *fx, const float *fy, int nk, uint32_t skipx, uint32_t skipy,
-                       int border, hipStream_t s);
-
 static int conv_separable_impl(const zg_image *src, const zg_image *dst, const float *kx, uint32_t nkx,
                                const float *ky, uint32_t nky, int border, hipStream_t s) {
     int rc;
@@ -572,8 +517,8 @@ static int conv_separable_impl(const zg_image *src, const zg_image *dst, const f
         p.mode = MODE_F32;
         p.fx.assign(kx, kx + nkx);
         p.fy.assign(ky, ky + nky);
-        for (uint32_t i = 0; i < nkx && i < 32; ++i) if (std::fabs(kx[i]) < 1e-10f) p.skipx |= 1u << i;
-        for (uint32_t i = 0; i < nky && i < 32; ++i) if (std::fabs(ky[i]) < 1e-10f) p.skipy |= 1u << i;
+        p.skipx = skip_mask(kx, nkx);
+        p.skipy = skip_mask(ky, nky);
         if (src->pixel == ZG_PIXEL_F32 && p.nkx == p.nky) { // single-channel planes: four pixels per lane
             const int rcs = try_sep_tile_f32(src, dst, 1, p.fx.data(), p.fy.data(), p.nkx, p.skipx, p.skipy, border, s); // one wave per tile, no LDS
             if (rcs >= 0) return rcs;
@@ -667,11 +612,7 @@ static int conv_separable_planes_impl(const zg_image *src, const zg_image *dst, 
     while (p < n) {
         uint32_t run = 1; // planes p .. p + run - 1 share a launch
         if (src[p].pixel == ZG_PIXEL_F32 && nkx == nky && src[p].rows && src[p].cols) {
-            uint32_t skipx = 0, skipy = 0;
-            for (uint32_t i = 0; i < nkx && i < 32; ++i) {
-                if (std::fabs(kx[i]) < 1e-10f) skipx |= 1u << i;
-                if (std::fabs(ky[i]) < 1e-10f) skipy |= 1u << i;
-            }
+            const uint32_t skipx = skip_mask(kx, nkx), skipy = skip_mask(ky, nky); // nkx == nky here
             while (run < SF_MAX_PLANES && p + run < n && src[p + run].pixel == ZG_PIXEL_F32 && src[p + run].rows == src[p].rows &&
                    src[p + run].cols == src[p].cols && src[p + run].stride == src[p].stride && dst[p + run].stride == dst[p].stride)
                 ++run;
@@ -688,8 +629,6 @@ static int conv_separable_planes_impl(const zg_image *src, const zg_image *dst, 
     }
     return ZG_OK;
 }
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
 
 } // namespace zg
 
@@ -710,13 +649,7 @@ int zg_conv_separable_host(const zg_image *src, const zg_image *dst, const float
         });
         if (brc >= 0) return brc;
     }
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = conv_separable_impl(&a.dev, &b.dev, kx, nkx, ky, nky, border, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return conv_separable_impl(a, b, kx, nkx, ky, nky, border, nullptr); });
 }
 
 int zg_conv_separable_planes(const zg_image *src, const zg_image *dst, uint32_t n_planes, const float *kx, uint32_t nkx,
@@ -742,6 +675,14 @@ int zg_gaussian_kernel(float sigma, float *taps, uint32_t capacity) {
     return (int)size;
 }
 
+// gaussianBlur's taps for a sigma > 0 (image.zig:973-990), sized by the kernel's own size query.
+static int gaussian_taps(float sigma, std::vector<float> &taps) {
+    const int n = zg_gaussian_kernel(sigma, nullptr, 0);
+    if (n < 0) return -n;
+    taps = std::vector<float>((size_t)n);
+    return zg_gaussian_kernel(sigma, taps.data(), (uint32_t)n) == n ? ZG_OK : ZG_ERR_INVALID_ARGUMENT;
+}
+
 static int gaussian_impl(const zg_image *src, const zg_image *dst, float sigma, hipStream_t s) {
     int rc;
     if ((rc = check_image(src, "src")) || (rc = check_image(dst, "dst"))) return rc;
@@ -749,11 +690,10 @@ static int gaussian_impl(const zg_image *src, const zg_image *dst, float sigma, 
                "gaussianBlur: %ux%u vs %ux%u", src->rows, src->cols, dst->rows, dst->cols);
     if (sigma == 0) return copy_impl(src, dst, s);                       // image.zig:966
     ZG_REQUIRE(sigma > 0, ZG_ERR_INVALID_ARGUMENT, "gaussianBlur: InvalidSigma (%g)", sigma); // image.zig:970
-    const int n = zg_gaussian_kernel(sigma, nullptr, 0);
-    if (n < 0) return -n;
-    std::vector<float> taps((size_t)n);
-    if (zg_gaussian_kernel(sigma, taps.data(), (uint32_t)n) != n) return ZG_ERR_INVALID_ARGUMENT;
-    return conv_separable_impl(src, dst, taps.data(), (uint32_t)n, taps.data(), (uint32_t)n, ZG_BORDER_MIRROR, s);
+    std::vector<float> taps;
+    if ((rc = gaussian_taps(sigma, taps))) return rc;
+    const uint32_t n = (uint32_t)taps.size();
+    return conv_separable_impl(src, dst, taps.data(), n, taps.data(), n, ZG_BORDER_MIRROR, s);
 }
 
 int zg_gaussian_blur(const zg_image *src, const zg_image *dst, float sigma, zg_stream stream) {
@@ -774,28 +714,21 @@ int zg_gaussian_blur_planes(const zg_image *src, const zg_image *dst, uint32_t n
         ZG_REQUIRE(src[p].rows == dst[p].rows && src[p].cols == dst[p].cols, ZG_ERR_DIMENSION_MISMATCH,
                    "gaussianBlur: plane %u is %ux%u vs %ux%u", p, src[p].rows, src[p].cols, dst[p].rows, dst[p].cols);
     }
-    const int n = zg_gaussian_kernel(sigma, nullptr, 0);
-    if (n < 0) return -n;
-    std::vector<float> taps((size_t)n);
-    if (zg_gaussian_kernel(sigma, taps.data(), (uint32_t)n) != n) return ZG_ERR_INVALID_ARGUMENT;
-    return conv_separable_planes_impl(src, dst, n_planes, taps.data(), (uint32_t)n, taps.data(), (uint32_t)n, ZG_BORDER_MIRROR, s);
+    std::vector<float> taps;
+    if (int rc = gaussian_taps(sigma, taps)) return rc;
+    const uint32_t n = (uint32_t)taps.size();
+    return conv_separable_planes_impl(src, dst, n_planes, taps.data(), n, taps.data(), n, ZG_BORDER_MIRROR, s);
 }
 
 int zg_gaussian_blur_host(const zg_image *src, const zg_image *dst, float sigma) {
     if (sigma > 0) { // gaussianBlur is convolveSeparable(.mirror) with ceil(3 sigma) rows of halo (image.zig:973-994)
-        const int n = zg_gaussian_kernel(sigma, nullptr, 0);
+        const int n = zg_gaussian_kernel(sigma, nullptr, 0); // the size only: a sigma it refuses is refused below, by the whole-frame call
         if (n > 0) {
             const int brc = host_banded(src, dst, (uint32_t)n / 2, [&](const zg_image *sv, const zg_image *dv, hipStream_t s) { return gaussian_impl(sv, dv, sigma, s); });
             if (brc >= 0) return brc;
         }
     }
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = gaussian_impl(&a.dev, &b.dev, sigma, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return gaussian_impl(a, b, sigma, nullptr); });
 }
 
 } // extern "C"

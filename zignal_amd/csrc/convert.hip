@@ -13,7 +13,7 @@
 // is the musl cbrtf algorithm Zig ports — two Newton steps in f64, one final rounding — written out here.
 // For float-typed RGB sources gammaToLinear needs pow on the device: restated below (exp/log based, as Zig's
 // port of Go's Pow); like the oracle's it is parity-unpinned against real Zig at the last ulp.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include <algorithm>
 #include "zg_hostmath.h"
 #include "zg_colordev.h"
@@ -371,9 +371,6 @@ static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **o
 
 static int space_channels(int space) { return space == ZG_CS_GRAY ? 1 : (space == ZG_CS_RGBA ? 4 : 3); }
 
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
-int convert_spaces_impl(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const float *srgb_lut_dev, hipStream_t s);
-
 // Gray(u8) -> Rgba(u8) (convertColor: r = g = b = grey, a = 255; the last step of the CLI's edges bridge, src/cli/edges.zig:133-135), four pixels per lane:
 // a dword in, sixteen bytes out. (k_convert<U8, Rgba(u8)>, a pixel per lane: 62 us for the 23 M pixels of 64 x 450 x 800 edge maps = 1.9 TB/s.)
 __global__ __launch_bounds__(256) void k_gray8_to_rgba8_4(DImg src, DImg dst) {
@@ -456,16 +453,12 @@ int convert_impl(const zg_image *src, int src_space, const zg_image *dst, int ds
 // 4 B written and 4 B read again, and a second launch. Fused: the resized pixel stays in a register and goes straight into
 // convertColor. Same arithmetic as k_resize_bilinear_rgba8 followed by k_convert (the two headers both kernels share), so the
 // result equals the two calls bit for bit. Algorithmic bytes: 16 read + 12 written per output pixel (28 B).
-int resize_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s);
 
 template <int MODE, int WAVES> // MODE as k_u8_to_lab4's; WAVES 4: four rows per workgroup in XCD-major order (round 4), 1: one-wave workgroups in address order
 __global__ __launch_bounds__(64 * WAVES) void k_resize_bilinear_rgba8_to_lab(DImg src, DImg dst, float ratio_x, float ratio_y, int tiles_x, const float *srgb_lut, FrameSpan fr) {
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     int wg = blockIdx.x;
-    if constexpr (WAVES == 4) {
-        const int nwg = gridDim.x, per_xcd = nwg >> 3;
-        if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
-    }
+    if constexpr (WAVES == 4) wg = xcd_major(wg, (int)gridDim.x);
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame; // a batch of equally shaped frames in one launch (batch.hip)
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     const int tyi = wg / tiles_x, txi = wg - tyi * tiles_x;
@@ -634,15 +627,8 @@ int zg_convert_host(const zg_image *src, int src_space, const zg_image *dst, int
         const int brc = host_banded(src, dst, 0, [&](const zg_image *sv, const zg_image *dv, hipStream_t s) { return convert_impl(sv, src_space, dv, dst_space, srgb_lut, s); });
         if (brc >= 0) return brc;
     }
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = convert_impl(&a.dev, src_space, &b.dev, dst_space, srgb_lut, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return convert_impl(a, src_space, b, dst_space, srgb_lut, nullptr); });
 }
-
 
 // Diagnostics: the device's own maths functions (zg_devmath.h) applied element-wise to device arrays, so that the
 // transcendental boundary of DESIGN.md section 4 can be swept densely against the oracle's restatement (tests/test_math_pin.py).
@@ -668,13 +654,7 @@ int zg_resize_convert(const zg_image *src, int src_space, const zg_image *dst, i
     return resize_convert_impl(src, src_space, dst, dst_space, method, srgb_lut, as_stream(stream));
 }
 int zg_resize_convert_host(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const zg_method *method, const float *srgb_lut) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = resize_convert_impl(&a.dev, src_space, &b.dev, dst_space, method, srgb_lut, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return resize_convert_impl(a, src_space, b, dst_space, method, srgb_lut, nullptr); });
 }
 
 } // extern "C"

@@ -5,7 +5,7 @@
 // tap including the zero ones, separate mul and add: src/image/convolution.zig:158-169) -> sqrt(gx^2 + gy^2) / 4 ->
 // @trunc(@max(0, @min(255, .))). The reference materialises three full f32 planes; here a workgroup stages the grey values
 // of its 64 x 4 tile plus a one-pixel replicate halo in LDS and writes only the u8 result: traffic = source once + 1 B/px.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_hostmath.h"
 
 #include <cmath>
@@ -15,10 +15,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int try_sobel_stream(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s); // sobel_stream.hip
-
-int try_sep_f32long_grey(const zg_image *src, const zg_image *dst, const float *fx, int nkx, const float *fy, int nky, int border, hipStream_t s); // conv_sep_f32long.hip
 
 __device__ inline float gray_as_f32(uint8_t v) { return (float)v; }
 
@@ -55,9 +51,7 @@ __global__ __launch_bounds__(256) void k_sobel(DImg src, DImg dst, int tiles_x, 
     __shared__ uint8_t ob[TH][64];
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame; // a batch of equally shaped frames (zg_batch_pipeline's edges step)
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
     const int x0 = tx * 64, y0 = ty * TH;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -191,9 +185,7 @@ __global__ __launch_bounds__(256) void k_canny_nms(const float *blur, uint8_t *s
     __shared__ float b[TH + 4][68];   // blurred: tile row r, column c at [r + 2][c + 2]
     __shared__ float mag[TH + 2][68]; // magnitude: at [r + 1][c + 1]
     __shared__ uint8_t st[TH][64];
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
     const int x0 = tx * 64, y0 = ty * TH;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -691,12 +683,6 @@ static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, flo
 // chain per row / column: they run as one lane per chain with LDS transposes (rows) or coalesced strided walks (columns),
 // latency-bound like boxBlur's SAT. The histogram, its percentile and the thresholds stay on the device (integer atomics
 // and a one-workgroup kernel), so nothing but the hysteresis fixed-point test synchronises the stream.
-
-int sat_planes_impl(const zg_image *src, float *sat, hipStream_t s, bool integer_valued, size_t plane_stride = 0); // box_blur.hip (0: planes contiguous)
-int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_t *check, uint32_t rows, uint32_t cols, float smooth, hipStream_t s); // isef.hip
-bool isef_2d_applies(uint32_t rows, uint32_t cols);
-size_t isef_check_bytes(uint32_t rows, uint32_t cols);
-int sat_planes_multi(const zg_image *const *srcs, float *const *sats, int count, hipStream_t s); // box_blur.hip
 
 // The recursions along ROWS run as the column kernel on the transposed plane: a row chain needs lanes = rows, i.e. a transpose
 // through LDS per 64-column chunk inside a kernel with one wave per 64 rows (354 + 464 us per 4096^2 plane that way); two plain
@@ -1339,13 +1325,7 @@ extern "C" {
 int zg_sobel(const zg_image *src, const zg_image *dst, zg_stream stream) { return sobel_impl(src, dst, as_stream(stream)); }
 
 int zg_sobel_host(const zg_image *src, const zg_image *dst) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = sobel_impl(&a.dev, &b.dev, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return sobel_impl(a, b, nullptr); });
 }
 
 int zg_canny(const zg_image *src, const zg_image *dst, float sigma, float low_threshold, float high_threshold, zg_stream stream) {
@@ -1353,13 +1333,7 @@ int zg_canny(const zg_image *src, const zg_image *dst, float sigma, float low_th
 }
 
 int zg_canny_host(const zg_image *src, const zg_image *dst, float sigma, float low_threshold, float high_threshold) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = canny_impl(&a.dev, &b.dev, sigma, low_threshold, high_threshold, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return canny_impl(a, b, sigma, low_threshold, high_threshold, nullptr); });
 }
 
 int zg_isef_smooth(const zg_image *src, const zg_image *dst, float smooth, zg_stream stream) {
@@ -1402,13 +1376,7 @@ int zg_shen_castan(const zg_image *src, const zg_image *dst, float smooth, uint3
 
 int zg_shen_castan_host(const zg_image *src, const zg_image *dst, float smooth, uint32_t window_size, float high_ratio, float low_rel, int hysteresis,
                         int use_nms) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = shen_castan_impl(&a.dev, &b.dev, smooth, window_size, high_ratio, low_rel, hysteresis, use_nms, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return shen_castan_impl(a, b, smooth, window_size, high_ratio, low_rel, hysteresis, use_nms, nullptr); });
 }
 
 // ImagePyramid.build's per-level arithmetic (src/image/pyramid.zig:57-80). `scale` is pow(scale_factor, level) as the

@@ -127,20 +127,10 @@ int zg_autocontrast(const zg_image *img, float cutoff, zg_stream stream) { retur
 int zg_equalize(const zg_image *img, zg_stream stream) { return enhance_impl(img, true, 0.0f, as_stream(stream)); }
 
 int zg_autocontrast_host(const zg_image *img, float cutoff) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, true, true))) return rc;
-    if ((rc = enhance_impl(&a.dev, false, cutoff, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return enhance_impl(a, false, cutoff, nullptr); });
 }
 int zg_equalize_host(const zg_image *img) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, true, true))) return rc;
-    if ((rc = enhance_impl(&a.dev, true, 0.0f, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return enhance_impl(a, true, 0.0f, nullptr); });
 }
 
 } // extern "C"

@@ -19,7 +19,7 @@
 //                      (no NMS: k_fast_row_write, raster-order compaction of a row)
 // A batch of images (a pyramid's levels) runs the same three launches: a job table in the kernel arguments, workgroups of all
 // jobs in one grid, each finding its job from the per-stage first-workgroup table.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <vector>

@@ -17,7 +17,7 @@
 // Measured and rejected: staging each workgroup's source bounding box in LDS (wave/LDS min-max reduction, coalesced
 // rectangle load, taps via ds_read_b128) — 268-284 us vs 236 us for the direct gather on the 4096^2 RGBA f32 bicubic
 // warp: the reduction, two extra barriers and a dependent load phase cost more than the L1 traffic they remove.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_hostmath.h"
 #include "zg_sample.h"
 
@@ -29,13 +29,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
-int fill_outside_impl(const zg_image *img, const void *pixel_value, int l, int t, int r, int b, hipStream_t s);
-int set_border_impl(const zg_image *img, const uint32_t rect[4], const void *pixel_value, hipStream_t s);
-int resize_planes_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s);
-int resize_lanczos_weights_impl(const zg_image *src, const zg_image *dst, const float *wx, const float *wy, hipStream_t s);
-void lanczos_plane_weights(uint32_t src_n, uint32_t dst_n, float *w);
 
 enum : int { GEOM_RESIZE = 0, GEOM_PROJECTIVE = 1, GEOM_AFFINE = 2, GEOM_ROTATE = 3, GEOM_EXTRACT = 4 };
 
@@ -102,9 +95,7 @@ __global__ __launch_bounds__(256) void k_geom(DImg src, DImg dst, GeomParams g, 
     using Vec = typename P::Vec;
     // 64 x 4 destination tile per workgroup; workgroups numbered XCD-major so one XCD's L2 serves a
     // contiguous band of destination (hence, for smooth maps, of source) rows.
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame; // a batch of equally shaped frames, the same map for each (zg_batch_pipeline)
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
@@ -228,9 +219,7 @@ static int check_pair(const zg_image *src, const zg_image *dst, const char *op) 
 // (Staging the wave's two source rows in LDS instead of gathering bytes through L1 was built and measured: slower, 335 against
 // 312 us for the pyramid, profiles/r03_experiments.txt.)
 __global__ __launch_bounds__(256) void k_resize_bilinear_u8(DImg src, DImg dst, float rx, float ry, int tiles_x, FrameSpan fr, int dword_rows) {
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame;
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
@@ -318,9 +307,7 @@ __global__ __launch_bounds__(256) void k_resize_bilinear_u8(DImg src, DImg dst, 
 // take the byte-by-byte form. Integer arithmetic, the same expressions: bit-identical to the kernel above.
 template <int R>
 __global__ __launch_bounds__(256) void k_resize_bilinear_u8_rows(DImg src, DImg dst, float rx, float ry, int tiles_x, FrameSpan fr, int dword_rows) {
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame;
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
@@ -924,23 +911,13 @@ static int insert_impl(const zg_image *self, const zg_image *source, const float
 
 using namespace zg;
 
-// host-pointer wrappers: stage, run on the default stream, copy back
-#define ZG_HOST2(call)                                                   \
-    HostStage a, b;                                                      \
-    int rc;                                                              \
-    if ((rc = a.upload(src, true, false))) return rc;                    \
-    if ((rc = b.upload(dst, false, true))) return rc;                    \
-    if ((rc = (call))) return rc;                                        \
-    ZG_HIP(hipStreamSynchronize(nullptr));                               \
-    return b.finish();
-
 extern "C" {
 
 int zg_resize(const zg_image *src, const zg_image *dst, const zg_method *method, zg_stream stream) {
     return resize_impl(src, dst, method, as_stream(stream));
 }
 int zg_resize_host(const zg_image *src, const zg_image *dst, const zg_method *method) {
-    ZG_HOST2(resize_impl(&a.dev, &b.dev, method, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return resize_impl(a, b, method, nullptr); });
 }
 
 int zg_lanczos_plane_weights(uint32_t src_n, uint32_t dst_n, float *weights) {
@@ -952,21 +929,21 @@ int zg_resize_lanczos_weights(const zg_image *src, const zg_image *dst, const fl
     return resize_lanczos_weights_checked(src, dst, wx, wy, as_stream(stream));
 }
 int zg_resize_lanczos_weights_host(const zg_image *src, const zg_image *dst, const float *wx, const float *wy) {
-    ZG_HOST2(resize_lanczos_weights_checked(&a.dev, &b.dev, wx, wy, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return resize_lanczos_weights_checked(a, b, wx, wy, nullptr); });
 }
 
 int zg_letterbox(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t rect_out[4], zg_stream stream) {
     return letterbox_impl(src, dst, method, rect_out, as_stream(stream));
 }
 int zg_letterbox_host(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t rect_out[4]) {
-    ZG_HOST2(letterbox_impl(&a.dev, &b.dev, method, rect_out, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return letterbox_impl(a, b, method, rect_out, nullptr); });
 }
 
 int zg_warp(const zg_image *src, const zg_image *dst, int kind, const float *m, const zg_method *method, zg_stream stream) {
     return warp_impl(src, dst, kind, m, method, as_stream(stream));
 }
 int zg_warp_host(const zg_image *src, const zg_image *dst, int kind, const float *m, const zg_method *method) {
-    ZG_HOST2(warp_impl(&a.dev, &b.dev, kind, m, method, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return warp_impl(a, b, kind, m, method, nullptr); });
 }
 
 int zg_rotate_into(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a,
@@ -975,7 +952,7 @@ int zg_rotate_into(const zg_image *src, const zg_image *dst, float angle, float 
 }
 int zg_rotate_into_host(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a,
                         const zg_method *method, int border) {
-    ZG_HOST2(rotate_into_impl(&a.dev, &b.dev, angle, cos_a, sin_a, method, border, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return rotate_into_impl(a, b, angle, cos_a, sin_a, method, border, nullptr); });
 }
 
 int zg_rotate_bounds(uint32_t rows, uint32_t cols, float angle, float cos_a, float sin_a, uint32_t *out_rows, uint32_t *out_cols) {
@@ -996,7 +973,7 @@ int zg_extract(const zg_image *src, const zg_image *dst, const float rect[4], fl
 }
 int zg_extract_host(const zg_image *src, const zg_image *dst, const float rect[4], float angle, float cos_a, float sin_a,
                     const zg_method *method, int border) {
-    ZG_HOST2(extract_impl(&a.dev, &b.dev, rect, angle, cos_a, sin_a, method, border, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return extract_impl(a, b, rect, angle, cos_a, sin_a, method, border, nullptr); });
 }
 
 int zg_crop_dims(const float rect[4], uint32_t *out_rows, uint32_t *out_cols) {
@@ -1017,7 +994,7 @@ int zg_crop(const zg_image *src, const zg_image *dst, const float rect[4], zg_st
     return crop_impl(src, dst, rect, as_stream(stream));
 }
 int zg_crop_host(const zg_image *src, const zg_image *dst, const float rect[4]) {
-    ZG_HOST2(crop_impl(&a.dev, &b.dev, rect, nullptr))
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return crop_impl(a, b, rect, nullptr); });
 }
 
 int zg_insert(const zg_image *self, const zg_image *source, const float rect[4], float angle, float cos_a, float sin_a,

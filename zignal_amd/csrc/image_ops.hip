@@ -4,7 +4,7 @@
 //   setBorder       reference src/image.zig:198-229
 //   flipLeftRight / flipTopBottom   reference src/image/transforms.zig:28-44 (in place)
 // All bit-exact by construction.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include <algorithm>
 #include <cstring>
 
@@ -173,52 +173,27 @@ int zg_set_border(const zg_image *img, const uint32_t rect[4], const void *pixel
 }
 
 int zg_fill_host(const zg_image *img, const void *pixel_value) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, false, true))) return rc;
-    if ((rc = fill_outside_impl(&a.dev, pixel_value, 0, 0, 0, 0, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, false, [&](const zg_image *a) { return fill_outside_impl(a, pixel_value, 0, 0, 0, 0, nullptr); });
 }
 int zg_set_border_host(const zg_image *img, const uint32_t rect[4], const void *pixel_value) {
-    HostStage a;
-    int rc;
     ZG_REQUIRE(rect, ZG_ERR_INVALID_ARGUMENT, "setBorder: null rect");
-    if ((rc = a.upload(img, true, true))) return rc; // the inside of rect keeps its pixels
-    if ((rc = set_border_impl(&a.dev, rect, pixel_value, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return set_border_impl(a, rect, pixel_value, nullptr); }); // the inside of rect keeps its pixels
 }
 
 int zg_invert(const zg_image *img, zg_stream stream) { return invert_impl(img, as_stream(stream)); }
 int zg_invert_host(const zg_image *img) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, true, true))) return rc;
-    if ((rc = invert_impl(&a.dev, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return invert_impl(a, nullptr); });
 }
 
 int zg_flip_left_right(const zg_image *img, zg_stream stream) { return flip_impl(img, true, as_stream(stream)); }
 int zg_flip_top_bottom(const zg_image *img, zg_stream stream) { return flip_impl(img, false, as_stream(stream)); }
 
 int zg_flip_left_right_host(const zg_image *img) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, true, true))) return rc;
-    if ((rc = flip_impl(&a.dev, true, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return flip_impl(a, true, nullptr); });
 }
 
 int zg_flip_top_bottom_host(const zg_image *img) {
-    HostStage a;
-    int rc;
-    if ((rc = a.upload(img, true, true))) return rc;
-    if ((rc = flip_impl(&a.dev, false, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return a.finish();
+    return host_in_place(img, true, [&](const zg_image *a) { return flip_impl(a, false, nullptr); });
 }
 
 } // extern "C"

@@ -24,7 +24,7 @@
 // storers wrote: a device-scope fence and a barrier between the two).
 // Round 3 ran the row passes as two full-plane transposes around a column kernel whose chain wave did its own LDS reads (64 per
 // block), the b * x products and a global store per row: 137 us per direction + 23 us per transpose for a 4096^2 plane.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <cmath>

@@ -1482,12 +1482,7 @@ int zg_jpeg_decode(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits
     return no_throw([&] { return decode_impl(jpeg, len, limits, dst, dst_space, scan_limit_reached_out, as_stream(stream)); });
 }
 int zg_jpeg_decode_host(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits, const zg_image *dst, int dst_space, int *scan_limit_reached_out) {
-    HostStage d;
-    int rc;
-    if ((rc = d.upload(dst, false, true))) return rc;
-    if ((rc = no_throw([&] { return decode_impl(jpeg, len, limits, &d.dev, dst_space, scan_limit_reached_out, nullptr); }))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return d.finish();
+    return host_in_place(dst, false, [&](const zg_image *d) { return no_throw([&] { return decode_impl(jpeg, len, limits, d, dst_space, scan_limit_reached_out, nullptr); }); });
 }
 
 } // extern "C"

@@ -10,7 +10,7 @@
 // The reference loops fields outermost; sample positions do not depend on the field, so they are computed once per pixel
 // and every field accumulates its own sum in the same sample order: same bits. f32 arithmetic as written in the
 // reference (separate mul / add). Integer fields: @round, clamp to the type, @trunc.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include "zg_devmath.h"
@@ -22,8 +22,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
 
 template <int PIX> struct MbAcc {
     using P = Px<PIX>;
@@ -223,25 +221,13 @@ int zg_motion_blur_linear(const zg_image *src, const zg_image *dst, float angle,
     return motion_linear_impl(src, dst, angle, cos_a, sin_a, distance, stream);
 }
 int zg_motion_blur_linear_host(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a, uint32_t distance) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = motion_linear_impl(&a.dev, &b.dev, angle, cos_a, sin_a, distance, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return motion_linear_impl(a, b, angle, cos_a, sin_a, distance, nullptr); });
 }
 int zg_motion_blur_radial(const zg_image *src, const zg_image *dst, float center_x, float center_y, float strength, int spin, zg_stream stream) {
     return motion_radial_impl(src, dst, center_x, center_y, strength, spin, stream);
 }
 int zg_motion_blur_radial_host(const zg_image *src, const zg_image *dst, float center_x, float center_y, float strength, int spin) {
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = motion_radial_impl(&a.dev, &b.dev, center_x, center_y, strength, spin, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return motion_radial_impl(a, b, center_x, center_y, strength, spin, nullptr); });
 }
 
 } // extern "C"

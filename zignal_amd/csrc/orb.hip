@@ -18,7 +18,7 @@
 //                           ballots are the descriptor's four little-endian words
 // Scratch, worst case, with S = sum over the levels of 1 / scale^2 (3.2 at the defaults): S - 1 bytes per source pixel of level images,
 // 8 S of FAST list, FAST's own 2 S of score map and about S / 100 of cell counts: 35 bytes per source pixel at the defaults.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_devmath.h"
 #include "zg_hostmath.h"
 

@@ -9,13 +9,11 @@
 // min / max for the midpoint, and for the alpha-trimmed mean the two trim boundaries by bisection plus one pass of sums.
 // Cost ~ 8 (2r+1)^2 byte reads per channel: right for the radii these filters are used with (median 3x3 .. 7x7); the
 // window area and the rank / trim counts are constants of the call, computed on the host in f64 as the reference does.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <cmath>
 
 namespace zg {
-
-int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
 
 constexpr int OS_MAXR = 15;
 enum : int { OS_PERCENTILE = 0, OS_MIDPOINT = 1, OS_ALPHA_TRIMMED = 2 };
@@ -151,13 +149,7 @@ int zg_order_statistic_blur(const zg_image *src, const zg_image *dst, uint32_t r
 }
 int zg_order_statistic_blur_host(const zg_image *src, const zg_image *dst, uint32_t radius, int op, double param, int border) {
     ZG_REQUIRE(op >= OS_PERCENTILE && op <= OS_ALPHA_TRIMMED, ZG_ERR_INVALID_ARGUMENT, "order-statistic blur: op %d", op);
-    HostStage a, b;
-    int rc;
-    if ((rc = a.upload(src, true, false))) return rc;
-    if ((rc = b.upload(dst, false, true))) return rc;
-    if ((rc = order_stat_impl(&a.dev, &b.dev, radius, op, param, border, nullptr))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return b.finish();
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return order_stat_impl(a, b, radius, op, param, border, nullptr); });
 }
 
 } // extern "C"

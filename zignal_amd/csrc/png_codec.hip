@@ -1006,12 +1006,7 @@ int zg_png_decode(const uint8_t *png, size_t len, const zg_png_limits *limits, c
     return no_throw([&] { return decode_impl(png, len, limits, dst, dst_space, truncated_out, as_stream(stream)); });
 }
 int zg_png_decode_host(const uint8_t *png, size_t len, const zg_png_limits *limits, const zg_image *dst, int dst_space, int *truncated_out) {
-    HostStage d;
-    int rc;
-    if ((rc = d.upload(dst, false, true))) return rc;
-    if ((rc = no_throw([&] { return decode_impl(png, len, limits, &d.dev, dst_space, truncated_out, nullptr); }))) return rc;
-    ZG_HIP(hipStreamSynchronize(nullptr));
-    return d.finish();
+    return host_in_place(dst, false, [&](const zg_image *d) { return no_throw([&] { return decode_impl(png, len, limits, d, dst_space, truncated_out, nullptr); }); });
 }
 int zg_png_filter(const zg_image *src, int filter, uint8_t *filtered, zg_stream stream) { return filter_impl(src, filter, filtered, as_stream(stream)); }
 int zg_png_encode(const zg_image *src, int src_space, const zg_png_encode_options *options, uint8_t **out, size_t *out_len, zg_stream stream) {

@@ -21,7 +21,7 @@
 //
 // Instructions per output pixel ~ (s / 2) x (8 + 4 ND + ND reads) for step 2 and ~ 4 (HM + 1) + HM + 30 for step 3 (HM = the padded half width of the taps,
 // ND = ceil((2 HM + 5) / 4) dwords per window) against ~ (1 + 2 / s) x K x s^2 multiply-adds plus two trips through HBM before.
-#include "zg_common.h"
+#include "zg_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -78,11 +78,7 @@ __device__ __forceinline__ void pyr_tile_body(const PyrTileJobs &jobs, const Pyr
     constexpr int NQ = HM + 1;               // row pairs a column window spans when it starts on an even row
     // workgroup b runs on XCD b % 8: the tiles of one XCD are a run of neighbours (they share source lines — a tile's rows are 90 .. 270 bytes of 128-byte
     // lines — in that XCD's L2 instead of each L2 fetching them for itself)
-    int tile = (int)blockIdx.x - job.block0;
-    {
-        const int per_xcd = job.ntiles >> 3;
-        if (ZG_XCD_ORDER && tile < (per_xcd << 3)) tile = (tile & 7) * per_xcd + (tile >> 3);
-    }
+    const int tile = xcd_major((int)blockIdx.x - job.block0, job.ntiles);
     const int ty = tile / job.tiles_x, tx = tile - ty * job.tiles_x;
     const int rows = jobs.src.rows, cols = jobs.src.cols;
     const uint8_t *src = (const uint8_t *)jobs.src.data;

@@ -13,7 +13,7 @@
 // reference's arithmetic and caches them per geometry. The device kernel is pure integer (or f32 mul / add)
 // accumulation over interleaved pixels: channels are independent, so no split / merge pass exists here.
 // Per output pixel the kernel reads T x T source pixels and writes one: that is the algorithmic traffic.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_hostmath.h"
 #include "zg_bilinear_u8.h"
 
@@ -98,9 +98,7 @@ __global__ __launch_bounds__(256) void k_resize_planes(DImg src, DImg dst, AxisT
     dst.data = (uint8_t *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     using Vec = typename P::Vec;
     constexpr int C = P::C;
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    int wg = blockIdx.x;
-    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
     const int tyi = wg / tiles_x, txi = wg - tyi * tiles_x;
     const int c = txi * 64 + (int)(threadIdx.x & 63);
     const int r = __builtin_amdgcn_readfirstlane(tyi * 4 + (int)(threadIdx.x >> 6)); // one row per wave
@@ -354,10 +352,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_resize_bilinear_rgba8(DImg src, 
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     int wg = blockIdx.x;
-    if constexpr (XCD) {
-        const int nwg = gridDim.x, per_xcd = nwg >> 3;
-        if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
-    }
+    if constexpr (XCD) wg = xcd_major(wg, (int)gridDim.x);
     src.data = (char *)src.data + (size_t)blockIdx.y * fr.src_frame;
     dst.data = (char *)dst.data + (size_t)blockIdx.y * fr.dst_frame;
     const int tyi = wg / tiles_x, txi = wg - tyi * tiles_x;

@@ -20,7 +20,7 @@
 //
 // Preconditions (else k_sobel runs): source u8 or Rgba(u8), row bytes a multiple of 16, 16-byte aligned rows on both sides of the
 // Rgba form (4-byte aligned destination rows), at least 64 pixels per row and 16 rows.
-#include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_u8pack.h"
 #include "zg_stream.h"
 
@@ -67,9 +67,7 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
     constexpr int D = 3 * DM;     // source rows in flight = rows per unrolled block
     constexpr int NG = NPX + 2;   // grey columns a lane holds per row: x - 1 .. x + NPX
 
-    const uint32_t nwg = gridDim.x, per_xcd = nwg >> 3;
-    uint32_t w = blockIdx.x;
-    if (ZG_XCD_ORDER && w < (per_xcd << 3)) w = (w & 7) * per_xcd + (w >> 3);
+    const uint32_t w = xcd_major((uint32_t)blockIdx.x, (uint32_t)gridDim.x);
     const int sy = (int)(w / (uint32_t)a.strips_x), sx = (int)(w - (uint32_t)sy * (uint32_t)a.strips_x);
     const uint8_t *srcf = a.src + (size_t)blockIdx.y * a.src_frame;
     uint8_t *dstf = a.dst + (size_t)blockIdx.y * a.dst_frame;

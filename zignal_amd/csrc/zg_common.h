@@ -165,6 +165,12 @@ __device__ inline uint8_t clamp_u8_i32(int v) { return (uint8_t)(v < 0 ? 0 : (v 
 #ifndef ZG_XCD_ORDER
 #define ZG_XCD_ORDER 1
 #endif
+// Workgroup `wg` of `nwg`, renumbered: the first (nwg / 8) * 8 ids go XCD-major, the tail keeps its place. int or uint32_t, as the caller indexes.
+template <typename I> __device__ inline I xcd_major(I wg, I nwg) {
+    const I per_xcd = nwg >> 3;
+    if (ZG_XCD_ORDER && wg < (per_xcd << 3)) wg = (wg & 7) * per_xcd + (wg >> 3);
+    return wg;
+}
 
 // ---- launch helpers ------------------------------------------------------------------------
 inline unsigned ceil_div(unsigned a, unsigned b) { return (a + b - 1) / b; }
@@ -184,6 +190,26 @@ struct HostStage {
     int upload(const zg_image *h, bool copy_in, bool write_back);
     int finish();         // D2H if writeback
 };
+
+// The common shape of a host-pointer entry point: stage, run `op` on the device twins on the default stream, wait, copy back.
+// host_src_dst: src is copied in, dst is written back. host_in_place: one image, written back; `copy_in` when the op reads it.
+template <typename F> int host_src_dst(const zg_image *src, const zg_image *dst, F &&op) {
+    HostStage a, b;
+    int rc;
+    if ((rc = a.upload(src, true, false))) return rc;
+    if ((rc = b.upload(dst, false, true))) return rc;
+    if ((rc = op(&a.dev, &b.dev))) return rc;
+    ZG_HIP(hipStreamSynchronize(nullptr));
+    return b.finish();
+}
+template <typename F> int host_in_place(const zg_image *img, bool copy_in, F &&op) {
+    HostStage a;
+    int rc;
+    if ((rc = a.upload(img, copy_in, true))) return rc;
+    if ((rc = op(&a.dev))) return rc;
+    ZG_HIP(hipStreamSynchronize(nullptr));
+    return a.finish();
+}
 
 int check_image(const zg_image *im, const char *name, bool device_pointer = true);
 
@@ -209,44 +235,11 @@ struct FrameSpan {
     size_t src_frame, dst_frame;
 };
 constexpr uint32_t MAX_FRAMES_PER_LAUNCH = 65535; // gridDim.y
-int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);              // resize_planes.hip
-int resize_planes_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s); // resize_planes.hip
-int resize_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);       // geom.hip
-int warp_frames(const zg_image *src, const zg_image *dst, int kind, const float *mat, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame,
-                hipStream_t s);                                                                                                                        // geom.hip
-int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, int which, hipStream_t s); // conv_sep_bytes2.hip: several levels in three launches
-int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, hipStream_t s); // pyramid_tile.hip: a level per kernel, nothing but the level written
-int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32_t *taps, int nk, hipStream_t s); // conv_sep_bytes2.hip: blur + bilinear level, -1 = not this shape
-int box_blur_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, hipStream_t s);                   // box_blur.hip
-int motion_linear_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float cos_a, float sin_a, uint32_t distance,
-                         hipStream_t s);                                                                                                                 // motion.hip
-int motion_radial_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float center_x, float center_y, float strength,
-                         int spin, hipStream_t s);                                                                                                       // motion.hip
-int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);                                        // edges.hip
-int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int dst_space, uint32_t n, size_t src_frame, size_t dst_frame, const float *srgb_lut,
-                                hipStream_t s);                                                                                                       // convert.hip
-
-int fast_detect_compact(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t *const *pos, uint32_t *const *key,
-                        const uint32_t *capacities, uint32_t *const *counts, hipStream_t s); // fast.hip: FAST for ORB, 8-byte list entries
-
-// u8 separable convolution of a batch of equally sized frames laid out back to back, one wave per column strip
-// (conv_sep_stream.hip). Returns -1 when its preconditions do not hold: the caller falls back to the tiled kernels.
-struct StreamJob {
-    const void *src; void *dst;
-    uint32_t n_frames, rows, cols;
-    int sp;                                // bytes per pixel: 1, 3, 4
-    size_t src_pitch, dst_pitch;           // bytes between rows
-    size_t src_frame, dst_frame;           // bytes between frames
-    bool down2;                            // dst is (rows / 2) x (cols / 2): blur then 2:1 bilinear (sp == 4)
-};
-int try_sep_stream(const StreamJob &j, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
 
 // scratch blocks from the library's caching allocator, ordered on stream s (zg_runtime.cpp)
 int scratch_alloc(void **out, size_t bytes, hipStream_t s);
 int host_threads(); // ZIGNAL_HIP_HOST_THREADS, else min(16, hardware threads)
 void scratch_free(void *p, hipStream_t s);
-int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, const int32_t *ix, int nkx,
-                          const int32_t *iy, int nky, int border, hipStream_t s); // conv_sep_bytes2.hip
 size_t scratch_block_budget(); // bytes one long-lived scratch block may take so that a few of them stay cached (a quarter of the cache limit)
 
 // Graph capture (zg_runtime.cpp). capturing(s): `s` is recording a capture right now. refuse_under_capture: what a call that cannot be

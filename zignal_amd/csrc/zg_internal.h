@@ -1,0 +1,107 @@
+// zg_internal.h — every function that one .hip of libzignal_hip defines and another calls, declared once. The defining file
+// includes this header too, so a changed parameter or default argument fails to compile instead of failing to link (or worse).
+// A try_* function returns -1 when the call is not one of its shapes: the caller goes on to the next route.
+#pragma once
+#include "zg_common.h"
+
+namespace zg {
+
+// ---- image_ops.hip
+int copy_impl(const zg_image *src, const zg_image *dst, hipStream_t s);
+int fill_outside_impl(const zg_image *img, const void *pixel_value, int l, int t, int r, int b, hipStream_t s);
+int set_border_impl(const zg_image *img, const uint32_t rect[4], const void *pixel_value, hipStream_t s);
+
+// ---- geom.hip
+int resize_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s);
+int resize_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
+int warp_frames(const zg_image *src, const zg_image *dst, int kind, const float *mat, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame,
+                hipStream_t s);
+
+// ---- resize_planes.hip
+int resize_planes_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s);
+int resize_lanczos_weights_impl(const zg_image *src, const zg_image *dst, const float *wx, const float *wy, hipStream_t s);
+void lanczos_plane_weights(uint32_t src_n, uint32_t dst_n, float *w);
+int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
+int resize_planes_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
+
+// ---- convert.hip
+int convert_impl(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const float *srgb_lut, hipStream_t s);
+int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int dst_space, uint32_t n, size_t src_frame, size_t dst_frame, const float *srgb_lut,
+                                hipStream_t s);
+
+// ---- colorspaces.hip
+int convert_spaces_impl(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const float *srgb_lut_dev, hipStream_t s);
+
+// ---- the separable convolution's routes, tried in conv_separable.hip's order
+int try_sep_bytes(const zg_image *src, const zg_image *dst, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);                        // conv_sep_bytes.hip
+int try_sep_bytes2(const zg_image *src, const zg_image *dst, const int32_t *ix, int nkx, const int32_t *iy, int nky, int border, hipStream_t s);             // conv_sep_bytes2.hip
+int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, const int32_t *ix, int nkx,
+                          const int32_t *iy, int nky, int border, hipStream_t s);                                                                         // conv_sep_bytes2.hip
+int try_sep_f32long(const zg_image *src, const zg_image *dst, const float *fx, int nkx, const float *fy, int nky, int border, hipStream_t s);                // conv_sep_f32long.hip
+int try_sep_f32long_grey(const zg_image *src, const zg_image *dst, const float *fx, int nkx, const float *fy, int nky, int border, hipStream_t s);           // conv_sep_f32long.hip
+int try_sep_f32x4(const zg_image *src, const zg_image *dst, const float *fx, const float *fy, int nk, uint32_t skipx, uint32_t skipy,
+                  int border, hipStream_t s);                                                                                                             // conv_sep_f32x4.hip
+constexpr uint32_t SF_MAX_PLANES = 8; // planes per launch of conv_sep_tile_f32.hip
+int try_sep_tile_f32(const zg_image *src, const zg_image *dst, uint32_t n, const float *fx, const float *fy, int nk, uint32_t skipx, uint32_t skipy,
+                     int border, hipStream_t s);                                                                                                          // conv_sep_tile_f32.hip
+
+// u8 separable convolution of a batch of equally sized frames laid out back to back, one wave per column strip (conv_sep_stream.hip).
+struct StreamJob {
+    const void *src; void *dst;
+    uint32_t n_frames, rows, cols;
+    int sp;                                // bytes per pixel: 1, 3, 4
+    size_t src_pitch, dst_pitch;           // bytes between rows
+    size_t src_frame, dst_frame;           // bytes between frames
+    bool down2;                            // dst is (rows / 2) x (cols / 2): blur then 2:1 bilinear (sp == 4)
+};
+int try_sep_stream(const StreamJob &j, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
+
+// The tiled Rgba(u8) form of the same (conv_sep_rgba8.hip).
+struct Rgba8Batch { // frames laid out back to back
+    const void *src; void *dst;
+    uint32_t n_frames, rows, cols;
+    size_t src_stride, dst_stride;         // row strides in pixels
+    size_t src_frame_px, dst_frame_px;     // frame strides in pixels
+    bool down2;                            // dst is (rows/2) x (cols/2): blur then 2:1 bilinear
+};
+int try_sep_rgba8_batch(const Rgba8Batch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
+
+// ---- conv2d_stream.hip
+int try_conv2d_stream(const zg_image *src, const zg_image *dst, const float *taps, int kh, int kw, int border, hipStream_t s);
+
+// ---- box_blur.hip
+int sat_planes_impl(const zg_image *src, float *sat, hipStream_t s, bool integer_valued, size_t plane_stride = 0); // 0: planes contiguous
+int sat_planes_multi(const zg_image *const *srcs, float *const *sats, int count, hipStream_t s);
+int box_blur_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, hipStream_t s);
+
+// ---- box_fused.hip
+int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, bool sharpen, hipStream_t s);
+
+// ---- motion.hip
+int motion_linear_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float cos_a, float sin_a, uint32_t distance,
+                         hipStream_t s);
+int motion_radial_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float center_x, float center_y, float strength,
+                         int spin, hipStream_t s);
+
+// ---- edges.hip
+int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
+int resize_impl_bilinear_u8(const zg_image *src, const zg_image *dst, hipStream_t s); // what zg_resize(.bilinear) runs for a u8 plane
+
+// ---- sobel_stream.hip
+int try_sobel_stream(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
+
+// ---- isef.hip
+int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_t *check, uint32_t rows, uint32_t cols, float smooth, hipStream_t s);
+bool isef_2d_applies(uint32_t rows, uint32_t cols);
+size_t isef_check_bytes(uint32_t rows, uint32_t cols);
+
+// ---- the pyramid's levels
+int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, int which, hipStream_t s); // conv_sep_bytes2.hip: several levels in three launches
+int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, hipStream_t s); // pyramid_tile.hip: a level per kernel, nothing but the level written
+int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32_t *taps, int nk, hipStream_t s); // conv_sep_bytes2.hip: blur + bilinear level
+
+// ---- fast.hip: FAST for ORB, 8-byte list entries
+int fast_detect_compact(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t *const *pos, uint32_t *const *key,
+                        const uint32_t *capacities, uint32_t *const *counts, hipStream_t s);
+
+} // namespace zg
