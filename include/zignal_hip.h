@@ -730,4 +730,8 @@ ZG_API void zg_jpeg_free(void *p);
  * zig/zignal_hip_match.zig). */
 #include "zignal_hip_match.h"
 
+/* HoughTransform (src/image/hough.zig) on the edge maps above: a module of its own in the same way (_HOUGH_SIGNATURES,
+ * zig/zignal_hip_hough.zig). */
+#include "zignal_hip_hough.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -8,7 +8,7 @@
 //!     zig run -O ReleaseFast --dep zignal -Mroot=tools/zig_golden.zig -Mzignal=<zignal checkout>/src/root.zig > tests/golden/zig_golden.json
 //!     python -m pytest tests/test_zig_golden.py -q          # skipped while the file is absent
 //!
-//! (The zignal module is what the `matcher` section calls; every other section is std only.)
+//! (The zignal module is what the `matcher` and `hough` sections call; every other section is std only.)
 //!
 //! (ReleaseFast is what the reference's own CI and examples build with; Debug must give the same bits — none of this is fast-math.)
 //! Std only but for the matcher section: every expression below is the reference's own, restated with its file:line, so the numbers are those zignal computes
@@ -27,10 +27,13 @@
 //!   matcher                 BruteForceMatcher.match / knnMatch / radiusMatch of the zignal module itself on clustered descriptors with
 //!                           tied distances; each case carries its inputs [query bytes, train bytes] and parameters. Pins what a
 //!                           restatement cannot: that std.mem.sort keeps equal distances in train order   src/features/matcher.zig:44-212
+//!   hough                   HoughTransform of the zignal module itself: the cos / sin tables of init for sizes with and without a quarter
+//!                           point (the entries that rest on the last bit of Zig's f64 @cos / @sin), then compute and findLines on
+//!                           random edges, inputs included; the all-zero accumulator pins std.mem.sort's order of equal scores   src/image/hough.zig:38-257
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
-const zignal = @import("zignal"); // the matcher section alone
+const zignal = @import("zignal"); // the matcher and hough sections alone
 
 fn bits(x: f32) u32 {
     return @bitCast(x);
@@ -309,6 +312,67 @@ fn matcherSection(w: anytype, allocator: std.mem.Allocator) !void {
     try w.print("\n  ],\n", .{});
 }
 
+// ---- hough: the reference's own HoughTransform on inputs made here -------------------------------------------------------------
+fn printLines(w: anytype, lines: []const zignal.HoughTransform.Line) !void {
+    try w.print("[", .{});
+    for (lines, 0..) |l, i| try w.print("{s}[{d},{d},{d},{d},{d},{d},{d}]", .{ if (i == 0) "" else ",", bits(l.angle), bits(l.radius), l.score, bits(l.p1.x()), bits(l.p1.y()), bits(l.p2.x()), bits(l.p2.y()) });
+    try w.print("]", .{});
+}
+
+/// The tables of init for sizes with and without a quarter point (the only entries the last bit of @cos / @sin can move), then
+/// compute and findLines on random edges with three values, a box past the image's edge, and the all-zero tie-order accumulator.
+fn houghSection(w: anytype, allocator: std.mem.Allocator) !void {
+    const table_sizes = [_]u32{ 2, 3, 4, 5, 8, 9, 63, 64, 97, 126, 128, 130, 220, 250, 256, 300, 512, 1024, 2048 };
+    try w.print("  \"hough\": {{\"tables\": [", .{});
+    for (table_sizes, 0..) |size, si| {
+        var h = try zignal.HoughTransform.init(allocator, size);
+        defer h.deinit();
+        try w.print("{s}\n   {{\"size\": {d}, \"cos\": [", .{ if (si == 0) "" else ",", size });
+        for (h.cos_table, 0..) |v, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", v });
+        try w.print("], \"sin\": [", .{});
+        for (h.sin_table, 0..) |v, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", v });
+        try w.print("]}}", .{});
+    }
+    try w.print("\n  ], \"cases\": [", .{});
+    // size, image rows, image cols, box l, box t, one edge pixel in `sparsity`
+    const shapes = [_][6]u32{ .{ 2, 2, 2, 0, 0, 2 }, .{ 5, 5, 5, 0, 0, 2 }, .{ 9, 9, 9, 0, 0, 0 }, .{ 63, 70, 66, 2, 3, 8 }, .{ 64, 64, 64, 0, 0, 16 }, .{ 97, 110, 120, 20, 30, 24 } };
+    const nms = [_][2]f32{ .{ 10.0, 5.0 }, .{ 5.0, 5.0 }, .{ std.math.nan(f32), 5.0 }, .{ -1.0, -1.0 }, .{ std.math.inf(f32), std.math.inf(f32) }, .{ 180.0, 1.5 } };
+    for (shapes, 0..) |shape, si| {
+        var rng = Lcg{ .s = 60 + @as(u32, @intCast(si)) };
+        const size = shape[0];
+        var edges: zignal.Image(u8) = try .init(allocator, shape[1], shape[2]);
+        defer edges.deinit(allocator);
+        const values = [_]u8{ 1, 128, 255 };
+        for (edges.data) |*e| e.* = if (shape[5] != 0 and rng.next() % shape[5] == 0) values[rng.next() % 3] else 0; // sparsity 0: no edge at all, the tie-order case
+        var h = try zignal.HoughTransform.init(allocator, size);
+        defer h.deinit();
+        var acc: zignal.Image(u32) = try .init(allocator, size, size);
+        defer acc.deinit(allocator);
+        acc.fill(0);
+        h.compute(edges, .{ .l = shape[3], .t = shape[4], .r = shape[3] + size, .b = shape[4] + size }, acc);
+        try w.print("{s}\n   {{\"size\": {d}, \"rows\": {d}, \"cols\": {d}, \"box\": [{d},{d},{d},{d}], \"edges\": [", .{ if (si == 0) "" else ",", size, shape[1], shape[2], shape[3], shape[4], shape[3] + size, shape[4] + size });
+        for (edges.data, 0..) |e, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", e });
+        try w.print("], \"accumulator\": [", .{});
+        var max: u32 = 0;
+        for (acc.data, 0..) |v, i| {
+            try w.print("{s}{d}", .{ if (i == 0) "" else ",", v });
+            max = @max(max, v);
+        }
+        try w.print("], \"finds\": [", .{});
+        var first = true;
+        for ([_]u32{ 0, @max(1, max / 2), max + 1 }) |threshold| for (nms) |pair| {
+            const lines = try h.findLines(allocator, acc, threshold, runtime(pair[0]), runtime(pair[1]));
+            defer allocator.free(lines);
+            try w.print("{s}{{\"threshold\": {d}, \"angle_bits\": {d}, \"radius_bits\": {d}, \"lines\": ", .{ if (first) "" else ",", threshold, bits(pair[0]), bits(pair[1]) });
+            try printLines(w, lines);
+            try w.print("}}", .{});
+            first = false;
+        };
+        try w.print("]}}", .{});
+    }
+    try w.print("\n  ]}},\n", .{});
+}
+
 pub fn main(init: std.process.Init) !void {
     var buffer: [1 << 16]u8 = undefined;
     var stdout = std.Io.File.stdout().writer(init.io, &buffer);
@@ -399,6 +463,9 @@ pub fn main(init: std.process.Init) !void {
 
     // src/features/matcher.zig:44-212 through the zignal module
     try matcherSection(w, init.gpa);
+
+    // src/image/hough.zig:38-257 through the zignal module
+    try houghSection(w, init.gpa);
 
     // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
     // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])

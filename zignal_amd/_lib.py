@@ -122,6 +122,11 @@ class ZgMatchStatistics(C.Structure):
     _fields_ = [("total_matches", C.c_size_t), ("mean_distance", C.c_float), ("min_distance", C.c_float), ("max_distance", C.c_float)]
 
 
+class ZgHoughLine(C.Structure):
+    """zg_hough_line == HoughTransform.Line (src/image/hough.zig:13-25), field for field."""
+    _fields_ = [("angle", C.c_float), ("radius", C.c_float), ("score", C.c_uint32), ("p1", C.c_float * 2), ("p2", C.c_float * 2)]
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -339,6 +344,27 @@ _MATCH_RESTYPES = {"zg_matcher_default_params": None, "zg_match_train_chunk": C.
 MATCH_EXPORTED_SYMBOLS = tuple(_MATCH_SIGNATURES)
 
 
+# the Hough module: every symbol include/zignal_hip_hough.h declares
+_I32P = C.POINTER(C.c_int32)
+_HOUGH_SIGNATURES = {
+    "zg_hough_lds_max_size": [],
+    "zg_hough_pixel_chunk": [],
+    "zg_hough_tables_host": [C.c_uint32, _I32P, _I32P],
+    "zg_hough_create": [C.c_uint32, C.POINTER(C.c_void_p)],
+    "zg_hough_create_with_tables": [C.c_uint32, _I32P, _I32P, C.POINTER(C.c_void_p)],
+    "zg_hough_destroy": [C.c_void_p],
+    "zg_hough_size": [C.c_void_p],
+    "zg_hough_compute": [C.c_void_p, _IMG, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p],
+    "zg_hough_find_lines": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_uint32,
+                            C.c_void_p, C.c_void_p],
+    "zg_hough_compute_host": [C.c_void_p, _IMG, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t],
+    "zg_hough_find_lines_host": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_uint32, _U32P],
+}
+_HOUGH_RESTYPES = {"zg_hough_lds_max_size": C.c_uint32, "zg_hough_pixel_chunk": C.c_uint32, "zg_hough_size": C.c_uint32}
+HOUGH_EXPORTED_SYMBOLS = tuple(_HOUGH_SIGNATURES)
+HOUGH_MAX_SIZE, HOUGH_MAX_CANDIDATES = 32768, 1 << 20  # ZG_HOUGH_MAX_SIZE, ZG_HOUGH_MAX_CANDIDATES
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -347,7 +373,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES)):
+        for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
+                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

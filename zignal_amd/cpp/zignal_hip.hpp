@@ -747,4 +747,78 @@ struct BruteForceMatcher {
     }
 };
 
+// ---- image: HoughTransform (src/image/hough.zig) ----
+// HoughTransform (hough.zig:11-230): compute adds the votes of a size x size box of an edge map to a size x size accumulator, findLines
+// returns the reference's list of lines, order included, bit for bit.
+class HoughTransform {
+  public:
+    using Line = zg_hough_line; // hough.zig:13-25, field for field
+    static_assert(sizeof(Line) == 28, "zg_hough_line is 28 bytes");
+
+    explicit HoughTransform(uint32_t size) : size_(size) { check(zg_hough_create(size, &h_)); }          // init (:38-66)
+    HoughTransform(uint32_t size, const std::vector<int32_t> &cos_table, const std::vector<int32_t> &sin_table) : size_(size) {
+        if (cos_table.size() != size || sin_table.size() != size) throw InvalidArgument(ZG_ERR_INVALID_ARGUMENT, "HoughTransform: size entries a table");
+        check(zg_hough_create_with_tables(size, cos_table.data(), sin_table.data(), &h_));
+    }
+    HoughTransform(HoughTransform &&o) noexcept : h_(o.h_), size_(o.size_) { o.h_ = nullptr; }
+    HoughTransform &operator=(HoughTransform &&o) noexcept { if (this != &o) { release(); h_ = o.h_; size_ = o.size_; o.h_ = nullptr; } return *this; }
+    HoughTransform(const HoughTransform &) = delete;
+    HoughTransform &operator=(const HoughTransform &) = delete;
+    ~HoughTransform() { release(); }
+
+    uint32_t size() const { return size_; }
+    uint32_t evenSize() const { return size_ % 2 == 0 ? size_ : size_ - 1; }
+    zg_hough_t handle() const { return h_; }
+    static void tables(uint32_t size, std::vector<int32_t> &cos_table, std::vector<int32_t> &sin_table) {
+        cos_table.assign(size, 0);
+        sin_table.assign(size, 0);
+        check(zg_hough_tables_host(size, cos_table.data(), sin_table.data()));
+    }
+
+    // compute (:75-139): host images; the votes are added to `accumulator`, which the caller clears
+    void compute(const Image<uint8_t> &edges, const Rectangle<uint32_t> &box, const Image<uint32_t> &accumulator) const;
+    // findLines (:142-204) of a host accumulator. Repeated with more room when the candidates or lines outnumber the first guess.
+    std::vector<Line> findLines(const Image<uint32_t> &accumulator, uint32_t threshold, float angle_nms_thresh, float radius_nms_thresh) const;
+    // asynchronous device forms: every pointer is device memory; nothing is synchronised, both can be recorded into a graph
+    void computeInto(const DeviceImage<uint8_t> &edges, const Rectangle<uint32_t> &box, uint32_t *accumulator, size_t acc_stride, zg_stream stream = nullptr) const;
+    void findLinesInto(const uint32_t *accumulator, size_t acc_stride, uint32_t threshold, const uint32_t *threshold_device, float angle_nms_thresh,
+                       float radius_nms_thresh, uint32_t max_candidates, Line *lines, uint32_t capacity, uint32_t *counts, zg_stream stream = nullptr) const {
+        check(zg_hough_find_lines(h_, accumulator, acc_stride, threshold, threshold_device, angle_nms_thresh, radius_nms_thresh, max_candidates, lines,
+                                  capacity, counts, stream));
+    }
+
+  private:
+    void release() { if (h_) (void)zg_hough_destroy(h_); h_ = nullptr; }
+    zg_hough_t h_ = nullptr;
+    uint32_t size_ = 0;
+};
+
+// (Image<uint32_t> is a shape and a buffer here: u32 is no pixel type of the image ops, and none of them is instantiated for it)
+inline void HoughTransform::compute(const Image<uint8_t> &edges, const Rectangle<uint32_t> &box, const Image<uint32_t> &accumulator) const {
+    if (accumulator.rows != size_ || accumulator.cols != size_) throw DimensionMismatch(ZG_ERR_DIMENSION_MISMATCH, "HoughTransform::compute: accumulator"); // :77
+    const zg_image e = edges.desc();
+    check(zg_hough_compute_host(h_, &e, box.l, box.t, box.r, box.b, accumulator.data, accumulator.stride));
+}
+inline std::vector<HoughTransform::Line> HoughTransform::findLines(const Image<uint32_t> &accumulator, uint32_t threshold, float angle_nms_thresh,
+                                                                   float radius_nms_thresh) const {
+    if (accumulator.rows != size_ || accumulator.cols != size_) throw DimensionMismatch(ZG_ERR_DIMENSION_MISMATCH, "HoughTransform::findLines: accumulator");
+    uint32_t max_candidates = 4096, capacity = 256;
+    for (;;) {
+        std::vector<Line> out(capacity);
+        uint32_t counts[2] = {0, 0};
+        check(zg_hough_find_lines_host(h_, accumulator.data, accumulator.stride, threshold, angle_nms_thresh, radius_nms_thresh, max_candidates, out.data(),
+                                       capacity, counts));
+        if (counts[0] > ZG_HOUGH_MAX_CANDIDATES) throw Error(ZG_ERR_UNSUPPORTED, "HoughTransform::findLines: more than ZG_HOUGH_MAX_CANDIDATES candidates");
+        if (counts[0] > max_candidates) { max_candidates = counts[0]; continue; }
+        if (counts[1] > capacity) { capacity = counts[1]; continue; }
+        out.resize(counts[1]);
+        return out;
+    }
+}
+inline void HoughTransform::computeInto(const DeviceImage<uint8_t> &edges, const Rectangle<uint32_t> &box, uint32_t *accumulator, size_t acc_stride,
+                                        zg_stream stream) const {
+    const zg_image e = edges.desc();
+    check(zg_hough_compute(h_, &e, box.l, box.t, box.r, box.b, accumulator, acc_stride, stream));
+}
+
 } // namespace zignal

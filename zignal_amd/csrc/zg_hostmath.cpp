@@ -215,4 +215,86 @@ const float *lanczos3_lut() {
     return lut;
 }
 
+// ---- Zig's f64 cos and sin (its port of musl's __cos, __sin and __rem_pio2) restated for |x| < 2^20 pi/2; the Hough tables use [0, pi] ----
+namespace {
+double k_sin(double x, double y, int iy) {
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    const double z = x * x, w = z * z, r = S2 + z * (S3 + z * S4) + z * w * (S5 + z * S6), v = z * x;
+    if (iy == 0) return x + v * (S1 + z * r);
+    return x - ((z * (0.5 * y - v * r) - y) - v * S1);
+}
+double k_cos(double x, double y) {
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    const double z = x * x;
+    double w = z * z;
+    const double r = z * (C1 + z * (C2 + z * C3)) + w * w * (C4 + z * (C5 + z * C6));
+    const double hz = 0.5 * z;
+    w = 1.0 - hz;
+    return w + (((1.0 - w) - hz) + (z * r - x * y));
+}
+uint32_t high_word(double x) {
+    uint64_t u;
+    std::memcpy(&u, &x, 8);
+    return (uint32_t)(u >> 32);
+}
+// the medium path of __rem_pio2 (|x| < 2^20 pi/2), which the special cases below 9 pi/4 reduce to step for step
+int rem_pio2(double x, double *y) {
+    const double toint = 1.5 / 2.220446049250313e-16, pio4 = 0x1.921fb54442d18p-1, invpio2 = 6.36619772367581382433e-01,
+                 pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11, pio2_2 = 6.07710050630396597660e-11,
+                 pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21, pio2_3t = 8.47842766036889956997e-32;
+    const uint32_t ix = high_word(x) & 0x7fffffff;
+    double fn = x * invpio2 + toint - toint;
+    int n = (int)fn;
+    double r = x - fn * pio2_1, w = fn * pio2_1t;
+    if (r - w < -pio4) { // matters with directed rounding only
+        n--; fn--;
+        r = x - fn * pio2_1; w = fn * pio2_1t;
+    } else if (r - w > pio4) {
+        n++; fn++;
+        r = x - fn * pio2_1; w = fn * pio2_1t;
+    }
+    y[0] = r - w;
+    int ey = (int)(high_word(y[0]) >> 20 & 0x7ff);
+    const int ex = (int)(ix >> 20);
+    if (ex - ey > 16) {
+        double t = r;
+        w = fn * pio2_2; r = t - w; w = fn * pio2_2t - ((t - r) - w);
+        y[0] = r - w;
+        ey = (int)(high_word(y[0]) >> 20 & 0x7ff);
+        if (ex - ey > 49) {
+            t = r;
+            w = fn * pio2_3; r = t - w; w = fn * pio2_3t - ((t - r) - w);
+            y[0] = r - w;
+        }
+    }
+    y[1] = (r - y[0]) - w;
+    return n;
+}
+} // namespace
+
+double cos_f64(double x) {
+    const uint32_t ix = high_word(x) & 0x7fffffff;
+    if (ix <= 0x3fe921fb) return ix < 0x3e46a09e ? 1.0 : k_cos(x, 0.0);
+    double y[2];
+    switch (rem_pio2(x, y) & 3) {
+    case 0: return k_cos(y[0], y[1]);
+    case 1: return -k_sin(y[0], y[1], 1);
+    case 2: return -k_cos(y[0], y[1]);
+    default: return k_sin(y[0], y[1], 1);
+    }
+}
+double sin_f64(double x) {
+    const uint32_t ix = high_word(x) & 0x7fffffff;
+    if (ix <= 0x3fe921fb) return ix < 0x3e500000 ? x : k_sin(x, 0.0, 0);
+    double y[2];
+    switch (rem_pio2(x, y) & 3) {
+    case 0: return k_sin(y[0], y[1], 1);
+    case 1: return k_cos(y[0], y[1]);
+    case 2: return -k_sin(y[0], y[1], 1);
+    default: return -k_cos(y[0], y[1]);
+    }
+}
+
 }} // namespace zg::hostmath
