@@ -734,4 +734,7 @@ ZG_API void zg_jpeg_free(void *p);
  * zig/zignal_hip_hough.zig). */
 #include "zignal_hip_hough.h"
 
+/* Image(T).floodFill (src/image/flood_fill.zig): a module of its own in the same way (_FLOOD_SIGNATURES, zig/zignal_hip_flood.zig). */
+#include "zignal_hip_flood.h"
+
 #endif /* ZIGNAL_HIP_H */

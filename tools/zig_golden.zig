@@ -30,10 +30,14 @@
 //!   hough                   HoughTransform of the zignal module itself: the cos / sin tables of init for sizes with and without a quarter
 //!                           point (the entries that rest on the last bit of Zig's f64 @cos / @sin), then compute and findLines on
 //!                           random edges, inputs included; the all-zero accumulator pins std.mem.sort's order of equal scores   src/image/hough.zig:38-257
+//!   flood_fill              Image(T).floodFill of the zignal module itself on patchy frames of u8, f32, Rgb(u8) and Rgba(f32) past 64 pixels
+//!                           in both directions: every case carries its pixels as bytes, the seed, the options (the threshold as f64
+//!                           bits, the exact square root of a sum of squares and the f64 below it among them), the fill value and the
+//!                           filled image   src/image/flood_fill.zig:28-131
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
-const zignal = @import("zignal"); // the matcher and hough sections alone
+const zignal = @import("zignal"); // the matcher, hough and flood_fill sections alone
 
 fn bits(x: f32) u32 {
     return @bitCast(x);
@@ -373,6 +377,69 @@ fn houghSection(w: anytype, allocator: std.mem.Allocator) !void {
     try w.print("\n  ]}},\n", .{});
 }
 
+// ---- flood_fill: the reference's own Image(T).floodFill on inputs made here --------------------------------------------------------
+fn printBytes(w: anytype, bytes: []const u8) !void {
+    try w.print("[", .{});
+    for (bytes, 0..) |b, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", b });
+    try w.print("]", .{});
+}
+
+fn floodValue(comptime T: type, v: u32) T {
+    return switch (T) {
+        u8 => @intCast(100 + v),
+        f32 => 0.25 * @as(f32, @floatFromInt(v)),
+        zignal.Rgb(u8) => .{ .r = @intCast(100 + v), .g = 7, .b = @intCast(50 + (v & 1)) },
+        zignal.Rgba(f32) => .{ .r = 0.5, .g = 0.125 * @as(f32, @floatFromInt(v)), .b = 0.75, .a = 0.25 * @as(f32, @floatFromInt(v & 1)) },
+        else => unreachable,
+    };
+}
+
+/// One pixel type: patches three pixels wide of four levels with a tenth of the pixels redrawn, every threshold with both modes and
+/// both connectivities from a seed next to the corner of the first 64 x 64 tile.
+fn floodCases(comptime T: type, comptime name: []const u8, w: anytype, allocator: std.mem.Allocator, seed: u32, thresholds: []const f64, fill_value: T, first: *bool) !void {
+    const rows: u32 = 73;
+    const cols: u32 = 133;
+    var rng = Lcg{ .s = seed };
+    var src: zignal.Image(T) = try .init(allocator, rows, cols);
+    defer src.deinit(allocator);
+    var coarse: [(rows / 3 + 1) * (cols / 3 + 1)]u32 = undefined;
+    for (&coarse) |*v| v.* = rng.next() % 4;
+    for (0..rows) |r| for (0..cols) |c| {
+        src.at(r, c).* = floodValue(T, if (rng.next() % 10 == 0) rng.next() % 4 else coarse[(r / 3) * (cols / 3 + 1) + c / 3]);
+    };
+    try w.print("{s}\n   {{\"pixel\": \"{s}\", \"rows\": {d}, \"cols\": {d}, \"data\": ", .{ if (first.*) "" else ",", name, rows, cols });
+    first.* = false;
+    try printBytes(w, std.mem.sliceAsBytes(src.data));
+    try w.print(", \"fill\": ", .{});
+    try printBytes(w, std.mem.asBytes(&fill_value)[0..@sizeOf(T)]);
+    try w.print(", \"fills\": [", .{});
+    var first_fill = true;
+    for (thresholds) |threshold| for ([_]zignal.FloodFillOptions.ThresholdMode{ .seed, .neighbor }, 0..) |mode, mi| for ([_]zignal.FloodFillOptions.Connectivity{ .four, .eight }) |connectivity| {
+        var img = try src.dupe(allocator);
+        defer img.deinit(allocator);
+        try img.floodFill(allocator, 63, 64, fill_value, .{ .threshold = threshold, .connectivity = connectivity, .mode = mode });
+        try w.print("{s}\n    {{\"row\": 63, \"col\": 64, \"threshold_bits\": {d}, \"connectivity\": {d}, \"mode\": {d}, \"out\": ", .{ if (first_fill) "" else ",", @as(u64, @bitCast(threshold)), @intFromEnum(connectivity), mi });
+        try printBytes(w, std.mem.sliceAsBytes(img.data));
+        try w.print("}}", .{});
+        first_fill = false;
+    };
+    try w.print("]}}", .{});
+}
+
+fn floodSection(w: anytype, allocator: std.mem.Allocator) !void {
+    try w.print("  \"flood_fill\": [", .{});
+    var first = true;
+    const nan = std.math.nan(f64);
+    const inf = std.math.inf(f64);
+    const root2 = @sqrt(@as(f64, 2.0)); // Rgb(u8): r differs by 1 and b by 1
+    const step = @sqrt(@as(f64, 0.125 * 0.125 + 0.25 * 0.25)); // Rgba(f32): g differs by 0.125 and a by 0.25
+    try floodCases(u8, "u8", w, allocator, 81, &.{ 0.0, 1.0, 1.5, -0.0, -1.0, nan, inf }, 7, &first);
+    try floodCases(f32, "f32", w, allocator, 82, &.{ 0.0, 0.25, std.math.nextAfter(f64, 0.25, 0.0), inf }, -3.5, &first);
+    try floodCases(zignal.Rgb(u8), "rgb_u8", w, allocator, 83, &.{ 0.0, root2, std.math.nextAfter(f64, root2, 0.0), 2.0, nan }, .{ .r = 1, .g = 2, .b = 3 }, &first);
+    try floodCases(zignal.Rgba(f32), "rgba_f32", w, allocator, 84, &.{ 0.0, step, std.math.nextAfter(f64, step, 0.0), inf }, .{ .r = -1, .g = -2, .b = -3, .a = -4 }, &first);
+    try w.print("\n  ],\n", .{});
+}
+
 pub fn main(init: std.process.Init) !void {
     var buffer: [1 << 16]u8 = undefined;
     var stdout = std.Io.File.stdout().writer(init.io, &buffer);
@@ -466,6 +533,9 @@ pub fn main(init: std.process.Init) !void {
 
     // src/image/hough.zig:38-257 through the zignal module
     try houghSection(w, init.gpa);
+
+    // src/image/flood_fill.zig:28-131 through the zignal module
+    try floodSection(w, init.gpa);
 
     // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
     // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])

@@ -127,6 +127,14 @@ class ZgHoughLine(C.Structure):
     _fields_ = [("angle", C.c_float), ("radius", C.c_float), ("score", C.c_uint32), ("p1", C.c_float * 2), ("p2", C.c_float * 2)]
 
 
+class ZgFloodFillOptions(C.Structure):
+    """zg_flood_fill_options == FloodFillOptions (src/image/flood_fill.zig:5-26): connectivity 4 | 8, mode 0 seed | 1 neighbor."""
+    _fields_ = [("threshold", C.c_double), ("connectivity", C.c_int), ("mode", C.c_int)]
+
+
+FLOOD_MODE_SEED, FLOOD_MODE_NEIGHBOR = range(2)
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -364,6 +372,16 @@ _HOUGH_RESTYPES = {"zg_hough_lds_max_size": C.c_uint32, "zg_hough_pixel_chunk": 
 HOUGH_EXPORTED_SYMBOLS = tuple(_HOUGH_SIGNATURES)
 HOUGH_MAX_SIZE, HOUGH_MAX_CANDIDATES = 32768, 1 << 20  # ZG_HOUGH_MAX_SIZE, ZG_HOUGH_MAX_CANDIDATES
 
+# the flood-fill module: every symbol include/zignal_hip_flood.h declares
+_FLOOD_SIGNATURES = {
+    "zg_flood_fill_tile": [],
+    "zg_flood_fill_bound_host": [C.c_int, C.c_double, C.POINTER(C.c_double)],
+    "zg_flood_fill": [_IMG, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(ZgFloodFillOptions), C.c_void_p, C.c_void_p],
+    "zg_flood_fill_host": [_IMG, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ZgFloodFillOptions), _U32P],
+}
+_FLOOD_RESTYPES = {"zg_flood_fill_tile": C.c_uint32}
+FLOOD_EXPORTED_SYMBOLS = tuple(_FLOOD_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -374,7 +392,7 @@ def lib() -> C.CDLL:
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
-                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES)):
+                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

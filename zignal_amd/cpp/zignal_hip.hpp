@@ -76,6 +76,14 @@ struct Interpolation {                                                          
     static Interpolation lanczos() { return {ZG_INTERP_LANCZOS}; }
     zg_method c_method() const { return zg_method{kind, b, c, nullptr}; }
 };
+struct FloodFillOptions {                                                                // flood_fill.zig:5-26
+    enum class Connectivity { four = 4, eight = 8 };
+    enum class ThresholdMode { seed = ZG_FLOOD_MODE_SEED, neighbor = ZG_FLOOD_MODE_NEIGHBOR };
+    double threshold = 0;
+    Connectivity connectivity = Connectivity::four;
+    ThresholdMode mode = ThresholdMode::seed;
+    zg_flood_fill_options c_options() const { return zg_flood_fill_options{threshold, (int)connectivity, (int)mode}; }
+};
 template <typename T> struct Rectangle { T l, t, r, b; T width() const { return l >= r ? T(0) : r - l; } T height() const { return t >= b ? T(0) : b - t; } };
 struct ProjectiveTransform { float m[9]; };                                              // geometry/transforms.zig:197
 
@@ -235,6 +243,18 @@ template <template <typename> class Img, typename T> class Ops {
         const zg_image s = desc();
         const uint32_t r[4] = {rect.l, rect.t, rect.r, rect.b};
         run(zg_set_border, zg_set_border_host, &s, r, (const void *)&value);
+    }
+    // image.zig:831 -> flood_fill.zig:59, in place. An Image is filled synchronously and the number of filled pixels returned. A DeviceImage's
+    // fill is enqueued on stream() and 0 returned: seed_device, when not null, is two device words (row, col) read in place of row and col,
+    // filled_count_device a device word that receives the count. A seed outside the image throws InvalidArgument (error.OutOfBounds).
+    uint32_t floodFill(uint32_t row, uint32_t col, const T &fill_value, const FloodFillOptions &options = {}, const uint32_t *seed_device = nullptr,
+                       uint32_t *filled_count_device = nullptr) const {
+        const zg_image s = desc();
+        const zg_flood_fill_options o = options.c_options();
+        uint32_t filled = 0;
+        if constexpr (Derived::on_device) check(zg_flood_fill(&s, row, col, seed_device, (const void *)&fill_value, &o, filled_count_device, self().stream()));
+        else check(zg_flood_fill_host(&s, row, col, (const void *)&fill_value, &o, &filled));
+        return filled;
     }
     void flipLeftRight() const { const zg_image s = desc(); run(zg_flip_left_right, zg_flip_left_right_host, &s); }   // transforms.zig:28
     void flipTopBottom() const { const zg_image s = desc(); run(zg_flip_top_bottom, zg_flip_top_bottom_host, &s); }   // transforms.zig:36

@@ -7,6 +7,7 @@
 // of its 64 x 4 tile plus a one-pixel replicate halo in LDS and writes only the u8 result: traffic = source once + 1 B/px.
 #include "zg_internal.h"
 #include "zg_hostmath.h"
+#include "zg_unionfind.h"
 
 #include <cmath>
 #include <map>
@@ -280,40 +281,6 @@ __global__ __launch_bounds__(256) void k_canny_nms(const float *blur, uint8_t *s
 // The label plane is only touched where components cross tiles, and the two last passes read a byte per pixel.
 // (Round 1 united every pixel pair through global memory: 177 - 296 us of the detectors' time on 4096^2 noise; labelling tiles but
 // still writing a label per pixel and resolving every weak pixel in a separate pass took 149 us on canny's frame.)
-__device__ inline int cc_find(int *label, int x) {
-    int p = label[x];
-    while (p != x) { // path halving (plain stores: another lane can only have written a smaller ancestor)
-        const int gp = label[p];
-        if (gp != p) label[x] = gp;
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-template <bool PAIRED>
-__device__ inline void cc_unite_t(int *label, int a, int b) {
-    for (;;) {
-        if constexpr (PAIRED) { // cc_find of both at once: through global memory the two walks are independent chains of loads, and a union's
-                                // time is their latency (k_cc_border 91 -> 74 us on noise; in LDS the extra instructions cost more than they hide)
-            int pa = label[a], pb = label[b];
-            while (pa != a || pb != b) {
-                const int ga = label[pa], gb = label[pb];
-                if (pa != a) { if (ga != pa) label[a] = ga; a = pa; pa = ga; }
-                if (pb != b) { if (gb != pb) label[b] = gb; b = pb; pb = gb; }
-            }
-        } else {
-            a = cc_find(label, a);
-            b = cc_find(label, b);
-        }
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; } // a > b: hang a under b
-        const int old = atomicMin(&label[a], b);
-        if (old == a) return; // a was still a root: linked
-        a = old;              // someone re-rooted a in the meantime: retry from its new parent
-    }
-}
-__device__ inline void cc_unite(int *label, int a, int b) { cc_unite_t<false>(label, a, b); }        // LDS
-__device__ inline void cc_unite_global(int *label, int a, int b) { cc_unite_t<true>(label, a, b); }
 // Links to the row below (SW / S / SE; the upward directions are the same pairs seen from the other side). Links the run
 // structure already implies are skipped: with S a candidate, SW and SE hang off S's run, and S itself is implied when W and
 // SW are both candidates (the pixel to the left makes the same link); without S, SW is implied by W and SE by E.

@@ -260,6 +260,36 @@ class Image:
         self._call("set_border", C.byref(d), (C.c_uint32 * 4)(l, t, r, b), v)
         return self
 
+    def flood_fill(self, row: int, col: int, fill_value, threshold: float = 0.0, connectivity: int = 4, mode="seed", seed=None, count=None,
+                   options=None):
+        """Image.floodFill (src/image/flood_fill.zig:59-131), in place: the seed (row, col) and every pixel connected to it through
+        pixels within `threshold` (of the seed's value, mode "seed", or of the neighbour they are reached from, mode "neighbor") become
+        `fill_value`. `options` (a FloodFillOptions) replaces the three keyword values. A seed outside the image raises InvalidArgument.
+        Device images: asynchronous on the current stream, returns self. `seed`, when given, is a device tensor of two 32-bit words
+        (row, col) that the kernels read in place of `row` and `col` (outside the image: nothing changes); `count`, when given, is a
+        device tensor of at least four bytes that receives the number of filled pixels.
+        Host images: synchronous, returns the number of filled pixels."""
+        from .flood import FloodFillOptions
+        row, col = int(row), int(col)
+        if not (0 <= row < 1 << 32 and 0 <= col < 1 << 32):
+            raise L.InvalidArgument(L.ERR_INVALID_ARGUMENT, f"flood_fill: seed ({row}, {col}) is outside the image")
+        o = (options if options is not None else FloodFillOptions(threshold, connectivity, mode))._c()
+        d, v = self._desc(), self._pixel_value(fill_value)
+        if not self.on_device:
+            if seed is not None or count is not None:
+                raise ValueError("seed and count are device tensors: a host image takes neither")
+            n = C.c_uint32(0)
+            L.check(L.lib().zg_flood_fill_host(C.byref(d), row, col, v, C.byref(o), C.byref(n)))
+            return int(n.value)
+        for name, t, nbytes in (("seed", seed, 8), ("count", count, 4)):
+            if t is not None and not (_is_torch(t) and t.is_cuda and t.device == self.data.device and t.is_contiguous()
+                                      and t.numel() * t.element_size() >= nbytes):
+                raise ValueError(f"{name} is a contiguous tensor of at least {nbytes} bytes on the image's device")
+        with torch.cuda.device(self.data.device):
+            L.check(L.lib().zg_flood_fill(C.byref(d), row, col, C.c_void_p(seed.data_ptr()) if seed is not None else None, v, C.byref(o),
+                                          C.c_void_p(count.data_ptr()) if count is not None else None, self._stream()))
+        return self
+
     def copy(self, dst: Optional["Image"] = None) -> "Image":
         dst = self._like() if dst is None else self._wrap(dst)
         self._same_side(dst)
