@@ -103,7 +103,50 @@ def hand_made():
     out["angles34"] = (34, even)
     out["size3"] = (3, np.array([[0, 0, 0], [0, 4, 0], [0, 0, 0]], np.uint32))
     out["size2"] = (2, np.ones((2, 2), np.uint32))
+    out["trips259"] = (259, trip_boundaries(259))  # 257 interior cells a side: two trips, the second with one live thread
+    out["trips515"] = (515, trip_boundaries(515))  # 513: three trips
     return out
+
+
+TRIP_ROW = 100  # the row of trip_boundaries' plateaus
+
+
+def trip_marks(size):
+    """The rows and columns m that are the last cell of a 256-cell trip (interior cell m is index m - 1): m + 1 opens the next trip."""
+    return [m for m in (256, 512) if m < size - 2]
+
+
+def trip_boundaries(size):
+    """Zeros and a few dozen peaks for findLines' device loops, which walk the interior columns of a row and the interior rows 256 cells
+    a trip and carry a sum from trip to trip: candidates on both sides of every trip's end in a row and in the rows, empty rows
+    between candidate rows, one in the last interior row and column. Scores are distinct (the order is forced) but for two far-apart
+    pairs and the plateaus of TRIP_ROW, whose cells are neighbours and so must be equal to be candidates: the stable sort's path."""
+    acc = np.zeros((size, size), np.uint32)
+    last = size - 2
+    score = [3000]
+
+    def peak(r, c, value=None):
+        assert not acc[r - 1:r + 2, c - 1:c + 2].any(), (r, c)  # no neighbour: a lower peak next to a higher one is no candidate
+        acc[r, c] = score[0] if value is None else value
+        score[0] -= 5
+
+    for m in trip_marks(size):
+        acc[TRIP_ROW, m - 1:m + 3] = 5000 + m  # columns m - 1 .. m + 2; the last plateau ends on the border column, which is no candidate
+        peak(m, 40)           # the last row of a trip ...
+        peak(m, m - 2)
+        peak(m + 1, 90)       # ... and the first of the next
+        peak(m + 1, m + 1)    # size 259 and 515: the last interior row and column
+    assert acc[last, last] != 0
+    for r in (1, 37, 129, 254, 300, 400, 510):
+        if r < last:
+            for c in (2, 64 + r % 7, 131, 254, 300, 509, last):
+                if c <= last:
+                    peak(r, c)
+    peak(30, 20, 4000)
+    peak(200, 240, 4000)  # equal scores far apart: row-major order decides
+    peak(60, 200, 4100)
+    peak(60, 10, 4100)
+    return acc
 
 
 NAN, INF = float("nan"), float("inf")
@@ -125,6 +168,8 @@ def find_cases(lds_max_size: int, pixel_chunk: int):
     cases["angles34"] = (34, hm["angles34"][1], 1, 1.0, 1.0)
     cases["size3"] = (3, hm["size3"][1], 1, 10.0, 5.0)
     cases["size2"] = (2, hm["size2"][1], 0, 10.0, 5.0)
+    cases["trips259"] = (259, hm["trips259"][1], 1, 1.0, 1.0)  # a low threshold and narrow suppression: most candidates become lines
+    cases["trips515"] = (515, hm["trips515"][1], 1, 1.0, 1.0)
     for name, thr in (("random63", None), ("random64", None), ("random97", None), ("dense64", None), ("lines97_box_inside", None),
                       ("lines97_box_past_right", None), ("starts_non_zero", 1 << 31)):
         acc = want_accumulator(name, lds_max_size, pixel_chunk)

@@ -278,6 +278,15 @@ def create_line(size, angle, radius, score, counters):
     return angle, radius, score, p1, p2
 
 
+def candidate_mask(acc, size, threshold):
+    """:158-170 for every interior cell at once: [r - 1, c - 1] says whether cell (r, c) is a candidate (size >= 3)."""
+    a = acc.astype(np.int64)
+    # the 3 x 3 maximum around every interior cell, the cell itself included: no neighbour is strictly greater when it equals the cell
+    nb = np.max([a[1 + dr:size - 1 + dr, 1 + dc:size - 1 + dc] for dr in (-1, 0, 1) for dc in (-1, 0, 1)], axis=0)
+    inner = a[1:-1, 1:-1]
+    return (inner >= threshold) & (nb == inner)
+
+
 def find_lines(acc, size, threshold, angle_nms_thresh, radius_nms_thresh, counters=None):
     """findLines (:142-204) of a size x size accumulator: (number of candidates, HOUGH_LINE_DTYPE array)."""
     counters = Counter() if counters is None else counters
@@ -287,11 +296,10 @@ def find_lines(acc, size, threshold, angle_nms_thresh, radius_nms_thresh, counte
         counters["too_small"] += 1
         return 0, np.zeros(0, HOUGH_LINE_DTYPE)
     a = acc.astype(np.int64)
-    # the 3 x 3 maximum around every interior cell, the cell itself included: no neighbour is strictly greater when it equals the cell
-    nb = np.max([a[1 + dr:size - 1 + dr, 1 + dc:size - 1 + dc] for dr in (-1, 0, 1) for dc in (-1, 0, 1)], axis=0)
     inner = a[1:-1, 1:-1]
-    rows, cols = np.nonzero((inner >= threshold) & (nb == inner))  # row-major order
-    counters["plateau_candidates"] += int(((inner >= threshold) & (nb == inner) & (
+    is_cand = candidate_mask(acc, size, threshold)
+    rows, cols = np.nonzero(is_cand)  # row-major order
+    counters["plateau_candidates"] += int((is_cand & (
         np.sum([a[1 + dr:size - 1 + dr, 1 + dc:size - 1 + dc] == inner for dr in (-1, 0, 1) for dc in (-1, 0, 1)], axis=0) > 1)).sum())
     cands = []
     for r, c in zip((rows + 1).tolist(), (cols + 1).tolist()):

@@ -334,4 +334,6 @@ def test_flood_header_bindings_and_zig_file_declare_the_same_symbols():
     main = open(os.path.join(ROOT, "include", "zignal_hip.h")).read()
     assert main.index('#include "zignal_hip_hough.h"') < main.index('#include "zignal_hip_flood.h"')
     makefile = open(os.path.join(ROOT, "zignal_amd", "csrc", "Makefile")).read()
-    assert makefile.count("zignal_hip_flood.h") == 2 and "zg_unionfind.h" in makefile
+    # both object rules depend on every header of include/ and of csrc/
+    assert "$(wildcard ../../include/*.h)" in makefile and "$(wildcard *.h)" in makefile and makefile.count("$(HEADERS)") == 2
+    assert os.path.isfile(os.path.join(ROOT, "include", "zignal_hip_flood.h")) and os.path.isfile(os.path.join(ROOT, "zignal_amd", "csrc", "zg_unionfind.h"))

@@ -180,6 +180,21 @@ def test_the_shared_find_lines_cases_reach_the_branches_they_are_there_for():
     assert want["size3"][0] == 1 and want["size2"][0] == 0
     assert max(n for n, _, _ in want.values()) > 256  # more candidates than one workgroup of the sort holds
     assert want["acc_lines97_box_inside"][0] == 3  # the three drawn lines
+    # the 256-cell trips of the device's column and row loops: candidates on both sides of every trip's end, few enough for the reference's loops
+    for name, n_marks in (("trips259", 1), ("trips515", 2)):
+        size, acc, thr, _, _ = K.find_cases(*limits())[name]
+        n, lines, counters = want[name]
+        cand = R.candidate_mask(acc, size, thr)
+        marks, last = K.trip_marks(size), size - 2
+        assert len(marks) == n_marks and last == marks[-1] + 1, name
+        assert n == int(cand.sum()) and 24 <= n < 300 and len(lines) > n // 2 and counters["sort_ties"] >= 4, (name, n, len(lines))  # two pairs, a plateau
+        assert cand[last - 1, last - 1], name  # the last interior row and column
+        for m in marks:
+            in_row = [c for c in range(m - 1, m + 3) if c <= last]
+            assert all(cand[K.TRIP_ROW - 1, c - 1] for c in in_row) and {m, m + 1} <= set(in_row), (name, m)
+            assert cand[m - 1].any() and cand[m].any(), (name, m)  # rows m and m + 1
+        rows_with = np.nonzero(cand.any(axis=1))[0] + 1
+        assert (np.diff(rows_with) > 1).any() and rows_with[0] == 1, name  # empty rows between candidate rows
 
 
 def test_the_shared_compute_cases_cover_what_they_name():
@@ -284,7 +299,9 @@ def test_hough_header_bindings_and_zig_file_declare_the_same_symbols():
     assert zg.HOUGH_LINE_DTYPE.itemsize == 28 == ctypes.sizeof(L.ZgHoughLine)
     assert [zg.HOUGH_LINE_DTYPE.fields[n][1] for n in ("angle", "radius", "score", "p1", "p2")] == [0, 4, 8, 12, 20]
     assert zg.HoughLine._fields == ("angle", "radius", "score", "p1", "p2")
-    assert "zignal_hip_hough.h" in open(os.path.join(ROOT, "zignal_amd", "csrc", "Makefile")).read()
+    makefile = open(os.path.join(ROOT, "zignal_amd", "csrc", "Makefile")).read()  # both object rules depend on every header of include/
+    assert "$(wildcard ../../include/*.h)" in makefile and makefile.count("$(HEADERS)") == 2
+    assert os.path.isfile(os.path.join(ROOT, "include", "zignal_hip_hough.h"))
     header = open(os.path.join(ROOT, "include", "zignal_hip_hough.h")).read()
     assert f"#define ZG_HOUGH_MAX_SIZE {L.HOUGH_MAX_SIZE}u" in header and f"#define ZG_HOUGH_MAX_CANDIDATES {L.HOUGH_MAX_CANDIDATES}u" in header
     assert L.HOUGH_MAX_CANDIDATES >= 65536

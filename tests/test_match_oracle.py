@@ -318,7 +318,9 @@ def test_match_header_bindings_and_zig_file_declare_the_same_symbols():
     assert ctypes.sizeof(L.ZgMatch) == 12 and ctypes.sizeof(L.ZgMatcherParams) == 12
     assert ctypes.sizeof(L.ZgDescriptorSet) == 24 and L.ZgDescriptorSet.count.offset == 16
     assert ctypes.sizeof(L.ZgMatchStatistics) == 24
-    assert "zignal_hip_match.h" in open(os.path.join(ROOT, "zignal_amd", "csrc", "Makefile")).read()
+    makefile = open(os.path.join(ROOT, "zignal_amd", "csrc", "Makefile")).read()  # both object rules depend on every header of include/
+    assert "$(wildcard ../../include/*.h)" in makefile and makefile.count("$(HEADERS)") == 2
+    assert os.path.isfile(os.path.join(ROOT, "include", "zignal_hip_match.h"))
 
 
 def test_every_match_entry_point_has_a_graph_replay_test_or_a_reason():

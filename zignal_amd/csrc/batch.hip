@@ -128,18 +128,18 @@ int run_convert(const Frames &in, const Frames &out, const float *lut, hipStream
 // not scale), where the bridge's frame.convert(u8) maps [0, 1] to [0, 255] first; and frames a CONVERT step left in another colour space (Oklab, Lab, Hsv ...)
 // are not RGB at all. Those frames go through the bridge literally: one conversion launch to a grey u8 plane, the detector on that.
 int run_edges(const zg_step &st, const Frames &in_frames, const Frames &out, hipStream_t s) {
-    void *grey = nullptr, *bridged = nullptr;
+    ScratchBlock grey(s), bridged(s); // released in the reverse order
     const size_t plane = (size_t)in_frames.rows * in_frames.cols;
-    if (const int rc = scratch_alloc(&grey, plane * in_frames.n, s)) return rc;
+    if (const int rc = grey.alloc(plane * in_frames.n)) return rc;
     Frames in = in_frames;
     const bool direct = !pixel_is_float(in.pixel) && (in.space == ZG_CS_GRAY || in.space == ZG_CS_RGB || in.space == ZG_CS_RGBA);
     if (!direct) {
-        if (const int rc = scratch_alloc(&bridged, plane * in.n, s)) { scratch_free(grey, s); return rc; }
-        const Frames b8{bridged, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
-        if (const int rc = run_convert(in, b8, nullptr, s)) { scratch_free(bridged, s); scratch_free(grey, s); return rc; }
+        if (const int rc = bridged.alloc(plane * in.n)) return rc;
+        const Frames b8{bridged.p, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
+        if (const int rc = run_convert(in, b8, nullptr, s)) return rc;
         in = b8;
     }
-    const Frames g{grey, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
+    const Frames g{grey.p, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
     int rc = -1;
     if (st.edges == ZG_EDGES_SOBEL && in.n > 0) {
         const zg_image a = in.frame(0), b = g.frame(0);
@@ -152,8 +152,6 @@ int run_edges(const zg_step &st, const Frames &in_frames, const Frames &out, hip
             return zg_shen_castan(a, b, st.sigma, st.window, st.high, st.low, 1, st.use_nms, (zg_stream)s);
         });
     if (rc == ZG_OK) rc = run_convert(g, out, nullptr, s);
-    scratch_free(bridged, s);
-    scratch_free(grey, s);
     return rc;
 }
 
@@ -239,11 +237,11 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
     // cache (512 MiB by default), so both stay cached from call to call beside whatever else lives there.
     const size_t budget = std::min<size_t>((size_t)1 << 30, scratch_block_budget());
     const uint32_t group = widest ? (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, budget / widest)) : n_frames;
-    void *ping[2] = {nullptr, nullptr};
+    ScratchBlock ping[2]{ScratchBlock(s), ScratchBlock(s)};
     int rc = ZG_OK;
     if (widest) {
-        if ((rc = scratch_alloc(&ping[0], (size_t)group * widest, s))) return rc;
-        if (n_steps > 2 && (rc = scratch_alloc(&ping[1], (size_t)group * widest, s))) { scratch_free(ping[0], s); return rc; }
+        if ((rc = ping[0].alloc((size_t)group * widest))) return rc;
+        if (n_steps > 2 && (rc = ping[1].alloc((size_t)group * widest))) return rc;
     }
     for (uint32_t g0 = 0; g0 < n_frames && rc == ZG_OK; g0 += group) {
         const uint32_t gn = std::min(group, n_frames - g0);
@@ -257,7 +255,7 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
             if (i + 1 < n_steps) {
                 Frames two = shape[i + 2];
                 two.n = gn;
-                two.data = i + 2 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : ping[flip];
+                two.data = i + 2 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : (void *)ping[flip].p;
                 const int rf = run_fused_pair(steps[i], steps[i + 1], cur, two, s);
                 if (rf >= 0) {
                     rc = rf;
@@ -269,7 +267,7 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
             if (take == 1) {
                 Frames next = shape[i + 1];
                 next.n = gn;
-                next.data = i + 1 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : ping[flip];
+                next.data = i + 1 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : (void *)ping[flip].p;
                 const zg_step &st = steps[i];
                 switch (st.kind) {
                 case ZG_STEP_GAUSSIAN_BLUR: rc = run_blur(cur, next, st.sigma, s); break;
@@ -295,8 +293,7 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
             i += take;
         }
     }
-    scratch_free(ping[0], s);
-    scratch_free(ping[1], s);
+    ping[0].reset(); // the first block first (an array's destructors run from its end): the order of frees decides which block a captured graph reuses
     return rc;
 }
 
@@ -332,10 +329,11 @@ int zg_batch_blur_resize(const void *src_frames, uint32_t n_frames, uint32_t row
         }
     }
 
-    void *scratch = nullptr;
+    ScratchBlock block(s);
     int rc = ZG_OK;
     if (!taps.empty()) { // batched blur of every frame in one launch, then the reference's resize per frame
-        if ((rc = scratch_alloc(&scratch, (size_t)n_frames * in_px * ps, s))) return rc;
+        if ((rc = block.alloc((size_t)n_frames * in_px * ps))) return rc;
+        void *scratch = block.p;
         const StreamJob job{src_frames, scratch, n_frames, rows, cols, 4, (size_t)cols * 4, (size_t)cols * 4, in_px * 4, in_px * 4, false};
         rc = try_sep_stream(job, taps.data(), taps.data(), (int)taps.size(), ZG_BORDER_MIRROR, s);
         if (rc < 0) {
@@ -348,23 +346,20 @@ int zg_batch_blur_resize(const void *src_frames, uint32_t n_frames, uint32_t row
                 zg_image dst{(char *)dst_frames + (size_t)i * out_px * ps, out_cols, out_rows, out_cols, pixel};
                 rc = resize_impl(&tmp, &dst, method, s);
             }
-            scratch_free(scratch, s);
             return rc;
         }
-        scratch_free(scratch, s);
-        scratch = nullptr;
+        block.reset(); // before the general path's allocation, which may take this block from the cache
     }
 
     // general path: two scratch frames so frame i+1's blur may start while frame i's resize still reads its scratch
-    if ((rc = scratch_alloc(&scratch, 2 * in_px * ps, s))) return rc;
+    if ((rc = block.alloc(2 * in_px * ps))) return rc;
     for (uint32_t i = 0; i < n_frames && rc == ZG_OK; ++i) {
         zg_image src{(char *)src_frames + (size_t)i * in_px * ps, cols, rows, cols, pixel};
-        zg_image tmp{(char *)scratch + (size_t)(i & 1) * in_px * ps, cols, rows, cols, pixel};
+        zg_image tmp{block.p + (size_t)(i & 1) * in_px * ps, cols, rows, cols, pixel};
         zg_image dst{(char *)dst_frames + (size_t)i * out_px * ps, out_cols, out_rows, out_cols, pixel};
         rc = zg_gaussian_blur(&src, &tmp, sigma, stream);
         if (rc == ZG_OK) rc = resize_impl(&tmp, &dst, method, s);
     }
-    scratch_free(scratch, s);
     return rc;
 }
 

@@ -112,19 +112,20 @@ static int otsu_impl(const zg_image *src, const zg_image *dst, uint8_t *threshol
     if (threshold_host && (rc = refuse_under_capture(s, "zg_threshold_otsu with a threshold_out (it reads the threshold back to the host)"))) return rc;
     if (threshold_host) *threshold_host = 0;
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
-    char *scratch = nullptr;
-    if ((rc = scratch_alloc((void **)&scratch, 256 * sizeof(unsigned int) + 16, s))) return rc;
-    unsigned int *hist = (unsigned int *)scratch;
-    uint8_t *thr = (uint8_t *)(hist + 256);
-    if ((rc = fill_async(hist, 0, 256 * sizeof(unsigned int), s))) { scratch_free(scratch, s); return rc; }
+    ScratchBlock scratch(s); // [histogram][threshold]
+    unsigned int *hist;
+    uint8_t *thr;
+    scratch.take(hist, 256);
+    scratch.take(thr, 16);
+    if ((rc = scratch.alloc())) return rc;
+    if ((rc = fill_async(hist, 0, 256 * sizeof(unsigned int), s))) return rc;
     hipLaunchKernelGGL(k_hist_u8, dim3(ceil_div(src->cols, 64), ceil_div(src->rows, 64)), dim3(256), 0, s, dimg(src), hist);
     hipLaunchKernelGGL(k_otsu_threshold, dim3(1), dim3(64), 0, s, (const unsigned int *)hist, thr, (double)((size_t)src->rows * src->cols));
     hipLaunchKernelGGL(k_apply_threshold, dim3(ceil_div(src->cols, 256), src->rows), dim3(256), 0, s, dimg(src), dimg(dst), (const uint8_t *)thr);
-    rc = hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
+    rc = launch_ok("k_apply_threshold") ? ZG_ERR_HIP : ZG_OK;
     if (rc == ZG_OK && threshold_host) { // the return value of the reference's method: needs the stream to finish
         rc = download_pageable(threshold_host, thr, 1, s);
     }
-    scratch_free(scratch, s);
     if (rc == ZG_ERR_HIP) set_error("thresholdOtsu: HIP failure");
     return rc;
 }
@@ -135,13 +136,12 @@ static int adaptive_impl(const zg_image *src, const zg_image *dst, uint32_t radi
     ZG_REQUIRE(radius != 0, ZG_ERR_INVALID_ARGUMENT, "thresholdAdaptiveMean: InvalidRadius (0)");
     ZG_REQUIRE(radius < (1u << 30), ZG_ERR_INVALID_ARGUMENT, "thresholdAdaptiveMean: radius too large");
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
-    float *sat = nullptr;
-    if ((rc = scratch_alloc((void **)&sat, (size_t)src->rows * src->cols * sizeof(float), s))) return rc;
-    if ((rc = sat_planes_impl(src, sat, s, true)) == ZG_OK) {
-        hipLaunchKernelGGL(k_adaptive_mean, dim3(ceil_div(src->cols, 256), src->rows), dim3(256), 0, s, (const float *)sat, dimg(src), dimg(dst), (int)radius, c);
-        if (hipGetLastError() != hipSuccess) { rc = ZG_ERR_HIP; set_error("thresholdAdaptiveMean: launch failed"); }
-    }
-    scratch_free(sat, s);
+    ScratchBlock block(s);
+    if ((rc = block.alloc((size_t)src->rows * src->cols * sizeof(float)))) return rc;
+    float *sat = (float *)block.p;
+    if ((rc = sat_planes_impl(src, sat, s, true))) return rc;
+    hipLaunchKernelGGL(k_adaptive_mean, dim3(ceil_div(src->cols, 256), src->rows), dim3(256), 0, s, (const float *)sat, dimg(src), dimg(dst), (int)radius, c);
+    if (launch_ok("k_adaptive_mean")) { rc = ZG_ERR_HIP; set_error("thresholdAdaptiveMean: launch failed"); }
     return rc;
 }
 
@@ -181,17 +181,16 @@ static int morph_impl(const zg_image *src, const zg_image *dst, const uint8_t *k
     k.rows = (int)krows; k.cols = (int)kcols;
     for (uint32_t i = 0; i < krows * kcols; ++i) k.on[i] = kernel[i] != 0;
     const size_t n = (size_t)src->rows * src->cols;
-    uint8_t *scratch = nullptr;
-    if ((rc = scratch_alloc((void **)&scratch, 3 * n, s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc(3 * n))) return rc;
+    uint8_t *scratch = (uint8_t *)block.p;
     if (op == 0 || op == 1) morph_chain(src, dst, k, iterations, op == 1, scratch, scratch + n, s);
     else {
         const zg_image mid{scratch + 2 * n, src->cols, src->rows, src->cols, ZG_PIXEL_U8};
         morph_chain(src, &mid, k, iterations, op == 2, scratch, scratch + n, s);
         morph_chain(&mid, dst, k, iterations, op != 2, scratch, scratch + n, s);
     }
-    rc = hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
-    if (rc) set_error("morphology: launch failed");
-    scratch_free(scratch, s);
+    if (launch_ok("k_morph")) { rc = ZG_ERR_HIP; set_error("morphology: launch failed"); }
     return rc;
 }
 

@@ -622,27 +622,24 @@ static int sat_planes_frames_impl(const zg_image *src, float *sat, hipStream_t s
     // exact rows: carries of the 16-column strips (a small table), then prefix + chain + store in one pass over the source
     if (sat_fused_applies(src, integer_valued)) {
         const int nstrips = (int)ceil_div(src->cols, 16u);
-        float *carries = nullptr;
-        if (int rc = scratch_alloc((void **)&carries, (size_t)n_frames * src->rows * nstrips * C * sizeof(float), s)) return rc;
-        const int rc = dispatch_pixel(src->pixel, [&](auto tag) -> int {
+        ScratchBlock block(s);
+        if (int rc = block.alloc((size_t)n_frames * src->rows * nstrips * C * sizeof(float))) return rc;
+        float *carries = (float *)block.p;
+        return dispatch_pixel(src->pixel, [&](auto tag) -> int {
             constexpr int PIX = decltype(tag)::value;
             constexpr int PC = Px<PIX>::C;
             hipLaunchKernelGGL((k_strip_carries<PIX>), dim3(src->rows, n_frames), dim3(256), 0, s, dimg(src), carries, nstrips, src_frame);
             hipLaunchKernelGGL((k_sat_chain<PIX>), dim3(ceil_div((unsigned)nstrips, 4u), (unsigned)PC, n_frames), dim3(SAT_THREADS), 0, s, dimg(src), (const float *)carries, sat, pstride,
                                nstrips, src_frame, sat_frame);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         });
-        scratch_free(carries, s);
-        return rc;
     }
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         if (exact_rows) hipLaunchKernelGGL((k_sat_rows_exact<PIX>), dim3(src->rows, (unsigned)C), dim3(256), 0, s, dimg(src), sat);
         else hipLaunchKernelGGL((k_sat_rows<PIX>), dim3(ceil_div(src->rows, 64), (unsigned)C), dim3(64), 0, s, dimg(src), sat);
         hipLaunchKernelGGL(k_sat_cols, dim3(ceil_div(src->cols, 64), (unsigned)C), dim3(64), 0, s, sat, (int)src->rows, (int)src->cols);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
 }
 
@@ -662,8 +659,9 @@ int sat_planes_multi(const zg_image *const *srcs, float *const *sats, int count,
         return ZG_OK;
     }
     const int nstrips = (int)ceil_div(a->cols, 16u);
-    float *carries = nullptr;
-    if (int rc = scratch_alloc((void **)&carries, (size_t)count * a->rows * nstrips * sizeof(float), s)) return rc;
+    ScratchBlock block(s);
+    if (int rc = block.alloc((size_t)count * a->rows * nstrips * sizeof(float))) return rc;
+    float *carries = (float *)block.p;
     SatPlanes pl{};
     for (int i = 0; i < count; ++i) {
         pl.src[i] = dimg(srcs[i]);
@@ -672,9 +670,8 @@ int sat_planes_multi(const zg_image *const *srcs, float *const *sats, int count,
     }
     hipLaunchKernelGGL(k_strip_carries_planes, dim3(a->rows, (unsigned)count), dim3(256), 0, s, pl, carries, nstrips);
     hipLaunchKernelGGL(k_sat_chain_planes, dim3(ceil_div((unsigned)nstrips, 4u), (unsigned)count), dim3(SAT_THREADS), 0, s, pl, (const float *)carries, nstrips);
-    const hipError_t e = hipGetLastError();
-    scratch_free(carries, s);
-    if (e != hipSuccess) { set_error("integral image: launch failed: %s", hipGetErrorString(e)); return ZG_ERR_HIP; }
+    const char *why = hipGetErrorString(hipPeekAtLastError()); // the message carries it; launch_ok clears the error
+    if (launch_ok("k_sat_chain_planes")) { set_error("integral image: launch failed: %s", why); return ZG_ERR_HIP; }
     return ZG_OK;
 }
 
@@ -752,7 +749,7 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
                 if constexpr (!std::is_same<typename Px<PIX>::Elem, float>::value) {
                     if (sharpen) hipLaunchKernelGGL((k_box_direct<PIX, true>), grid, dim3(256), 0, s, dimg(src), dimg(dst), (int)radius);
                     else hipLaunchKernelGGL((k_box_direct<PIX, false>), grid, dim3(256), 0, s, dimg(src), dimg(dst), (int)radius);
-                    ZG_HIP(hipGetLastError());
+                    if (const int e = launch_ok()) return e;
                 }
                 return ZG_OK;
             });
@@ -769,8 +766,9 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
     uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(n, scratch_block_budget() / (sat_frame * sizeof(float))));
     group = std::min<uint32_t>(group, 65535u / zpf);
     if (!sat_fused_applies(src, false)) group = 1;
-    float *sat = nullptr;
-    if ((rc = scratch_alloc((void **)&sat, (size_t)group * sat_frame * sizeof(float), s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc((size_t)group * sat_frame * sizeof(float)))) return rc;
+    float *sat = (float *)block.p;
     for (uint32_t f0 = 0; f0 < n && rc == ZG_OK; f0 += group) {
         const uint32_t k = std::min(group, n - f0);
         const zg_image a = frame_of(src, src_frame, f0), b = frame_of(dst, dst_frame, f0);
@@ -783,11 +781,9 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
             else if (buf) hipLaunchKernelGGL((k_box_mean<PIX, false, true>), grid, dim3(256), 0, s, (const float *)sat, plane, dimg(&a), dimg(&b), (int)radius, sat_frame, fr, (int)zpf);
             else if (sharpen) hipLaunchKernelGGL((k_box_mean<PIX, true, false>), grid, dim3(256), 0, s, (const float *)sat, plane, dimg(&a), dimg(&b), (int)radius, sat_frame, fr, (int)zpf);
             else hipLaunchKernelGGL((k_box_mean<PIX, false, false>), grid, dim3(256), 0, s, (const float *)sat, plane, dimg(&a), dimg(&b), (int)radius, sat_frame, fr, (int)zpf);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         });
     }
-    scratch_free(sat, s);
     return rc;
 }
 

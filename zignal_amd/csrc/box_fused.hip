@@ -871,25 +871,26 @@ int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t s
     if ((size_t)src->rows * (overlap ? (size_t)src->cols + 3 : (size_t)src->stride) * C + 64 >= (1ull << 32) || (size_t)src->rows * nk * C * sizeof(float) >= (1ull << 32)) return -1;
     zg_image from = *src;
     size_t from_frame = src_frame;
-    char *copy = nullptr;
+    ScratchBlock copy_block(s), K_block(s); // released in the reverse order: K before the copy
     int rc;
     if (overlap) {
         const size_t cstride = ((size_t)src->cols + 3) & ~(size_t)3; // pixels: rows start on dwords
         const size_t frame_bytes = (size_t)src->rows * cstride * px;
-        if ((rc = scratch_alloc((void **)&copy, (size_t)n * frame_bytes, s))) return rc;
+        if ((rc = copy_block.alloc((size_t)n * frame_bytes))) return rc;
+        char *copy = copy_block.p;
         for (uint32_t f = 0; f < n; ++f) {
             zg_image a = *src, b2 = *src;
             a.data = (char *)src->data + (size_t)f * src_frame;
             b2.data = copy + (size_t)f * frame_bytes;
             b2.stride = (uint32_t)cstride;
-            if ((rc = copy_impl(&a, &b2, s))) { scratch_free(copy, s); return rc; }
+            if ((rc = copy_impl(&a, &b2, s))) return rc;
         }
         from.data = copy;
         from.stride = (uint32_t)cstride;
         from_frame = frame_bytes;
     }
-    float *K = nullptr;
-    if ((rc = scratch_alloc((void **)&K, kbytes, s))) { if (copy) scratch_free(copy, s); return rc; }
+    if ((rc = K_block.alloc(kbytes))) return rc;
+    float *K = (float *)K_block.p;
 #ifdef BF_TIMING
     static unsigned long long *timing = nullptr;
     if (!timing) (void)hipMalloc((void **)&timing, 1024 * 16 * 2 * sizeof(unsigned long long));
@@ -914,7 +915,9 @@ int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t s
     };
     if (C == 4) by_radius(std::integral_constant<int, 4>{});
     else by_radius(std::integral_constant<int, 1>{});
-    const hipError_t e = hipGetLastError();
+    const char *why = hipGetErrorString(hipPeekAtLastError()); // the message carries it; launch_ok clears the error
+    rc = ZG_OK;
+    if (launch_ok("k_box_fused")) { set_error("boxBlur: launch failed: %s", why); rc = ZG_ERR_HIP; }
 #ifdef BF_TIMING
     {
         static int calls = 0;
@@ -930,10 +933,7 @@ int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t s
         }
     }
 #endif
-    scratch_free(K, s);
-    if (copy) scratch_free(copy, s);
-    if (e != hipSuccess) { set_error("boxBlur: launch failed: %s", hipGetErrorString(e)); return ZG_ERR_HIP; }
-    return ZG_OK;
+    return rc;
 }
 
 } // namespace zg

@@ -427,8 +427,7 @@ int convert_spaces_impl(const zg_image *src, int src_space, const zg_image *dst,
         return dispatch_pixel(dst->pixel, [&](auto dtag) -> int {
             constexpr int DPIX = decltype(dtag)::value;
             hipLaunchKernelGGL((k_convert_spaces<SPIX, DPIX>), grid, dim3(256), 0, s, dimg(src), dimg(dst), src_space, dst_space, srgb_lut_dev);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         });
     });
 }

@@ -197,8 +197,7 @@ static int launch_conv2d(const zg_image *src, const zg_image *dst, const Kernel2
         else ZG_C2(7, 7);
     } else ZG_C2(0, 0);
 #undef ZG_C2
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 static int convolve_impl(const zg_image *src, const zg_image *dst, const float *kernel, uint32_t kh, uint32_t kw, int border, hipStream_t s) {
@@ -248,23 +247,20 @@ static int convolve_impl(const zg_image *src, const zg_image *dst, const float *
             else return mode == 3 ? launch_conv2d<PIX, 3>(src, dst, k, border, s) : mode == 1 ? launch_conv2d<PIX, 1>(src, dst, k, border, s) : launch_conv2d<PIX, 2>(src, dst, k, border, s);
         });
     }
-    void *taps = nullptr; // larger: taps from device memory (uploaded synchronously: not capturable)
+    ScratchBlock block(s); // larger: taps from device memory (uploaded synchronously: not capturable)
     if ((rc = refuse_under_capture(s, "zg_convolve with more than 15 x 15 taps (the taps are uploaded from host memory)"))) return rc;
-    if ((rc = scratch_alloc(&taps, nk * 4, s))) return rc;
-    rc = upload_pageable(taps, is_float ? (const void *)kernel : (const void *)ik.data(), nk * 4, s);
-    if (rc == ZG_OK)
-        rc = dispatch_pixel(src->pixel, [&](auto tag) -> int {
-            constexpr int PIX = decltype(tag)::value;
-            const dim3 grid = row_grid(ceil_div(dst->cols, 256), dst->rows);
-            if constexpr (std::is_same<typename Px<PIX>::Elem, float>::value)
-                hipLaunchKernelGGL((k_conv2d_big<PIX, 0>), grid, dim3(256), 0, s, dimg(src), dimg(dst), (const void *)taps, (int)kh, (int)kw, border);
-            else
-                hipLaunchKernelGGL((k_conv2d_big<PIX, 2>), grid, dim3(256), 0, s, dimg(src), dimg(dst), (const void *)taps, (int)kh, (int)kw, border);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
-        });
-    scratch_free(taps, s);
-    return rc;
+    if ((rc = block.alloc(nk * 4))) return rc;
+    const void *taps = block.p;
+    if ((rc = upload_pageable(block.p, is_float ? (const void *)kernel : (const void *)ik.data(), nk * 4, s))) return rc;
+    return dispatch_pixel(src->pixel, [&](auto tag) -> int {
+        constexpr int PIX = decltype(tag)::value;
+        const dim3 grid = row_grid(ceil_div(dst->cols, 256), dst->rows);
+        if constexpr (std::is_same<typename Px<PIX>::Elem, float>::value)
+            hipLaunchKernelGGL((k_conv2d_big<PIX, 0>), grid, dim3(256), 0, s, dimg(src), dimg(dst), taps, (int)kh, (int)kw, border);
+        else
+            hipLaunchKernelGGL((k_conv2d_big<PIX, 2>), grid, dim3(256), 0, s, dimg(src), dimg(dst), taps, (int)kh, (int)kw, border);
+        return launch_ok();
+    });
 }
 
 } // namespace zg

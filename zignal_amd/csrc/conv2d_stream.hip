@@ -281,8 +281,7 @@ static int launch_c2s(const zg_image *src, const zg_image *dst, const float *tap
     const uint64_t items = (uint64_t)a.strips_x * a.strips_y;
     if (items > 0x7fffffffu) return -1;
     hipLaunchKernelGGL((k_conv2d_stream<SP, K, 1>), dim3((unsigned)items), dim3(64), 0, s, a, k);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // taps: round(k * 256) as floats, kh x kw. Returns -1 when the preconditions do not hold (the caller runs k_conv2d).

@@ -205,8 +205,7 @@ static int launch_bytes(const zg_image *src, const zg_image *dst, const int32_t 
     const int tiles_x = (int)ceil_div((uint32_t)(src->cols * SP), 1024u), tiles_y = (int)ceil_div(src->rows, 4 * RPT);
     hipLaunchKernelGGL((k_sep_bytes<SP, NK, RPT, CLAMP>), dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, dimg(src), dimg(dst), kx,
                        ky, border, tiles_x);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 template <int SP>

@@ -646,8 +646,9 @@ int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32
 
     const int row_bytes = (int)src->cols, half = nk / 2;
     const size_t temp_bytes = ((size_t)src->rows + 16) * row_bytes * 2; // + 16 slack rows: the column pass prefetches past a band's last row
-    uint32_t *temp = nullptr;
-    if (int rc = scratch_alloc((void **)&temp, temp_bytes, s)) return rc;
+    ScratchBlock block(s);
+    if (int rc = block.alloc(temp_bytes)) return rc;
+    uint32_t *temp = (uint32_t *)block.p;
     const int tiles_x = (int)ceil_div((uint32_t)row_bytes, 1024u);
     const int rows_per_wave = 4; // 1, 2 and 8 measured the same or worse (profiles/r05_experiments.txt)
     const B2Frames fr{0, 0, 0};
@@ -679,10 +680,7 @@ int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32
     a.nbands = src->rows <= (uint32_t)B2_R ? 1 : (int)ceil_div(src->rows - 1, (uint32_t)(B2_R - 1));
     if (wide) hipLaunchKernelGGL((k_cols_bilinear_u8<true>), dim3((unsigned)(a.tiles_x * a.nbands)), dim3(256), 0, s, a, tc);
     else hipLaunchKernelGGL((k_cols_bilinear_u8<false>), dim3((unsigned)(a.tiles_x * a.nbands)), dim3(256), 0, s, a, tc);
-    const hipError_t e = hipGetLastError();
-    scratch_free(temp, s);
-    ZG_HIP(e);
-    return ZG_OK;
+    return launch_ok("e");
 }
 
 // ---- the levels of a pyramid in three launches -----------------------------------------------------------------------------------------------------------
@@ -766,8 +764,9 @@ int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const flo
 
     const int row_bytes = (int)src->cols;
     const size_t temp_bytes = ((size_t)src->rows + 16) * row_bytes * 2, plane_bytes = (size_t)src->rows * src->cols;
-    uint8_t *block = nullptr;
-    if (int rc = scratch_alloc((void **)&block, temp_bytes * np + plane_bytes * n_dense, s)) return rc;
+    ScratchBlock scratch(s);
+    if (int rc = scratch.alloc(temp_bytes * np + plane_bytes * n_dense)) return rc;
+    uint8_t *block = (uint8_t *)scratch.p;
     RowsJobs rj{};
     DenseJobs dj{};
     FusedJobs fj{};
@@ -814,9 +813,7 @@ int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const flo
             rc = resize_impl_bilinear_u8(&tmp, &levels[dense_level[d]], s);
         }
     }
-    const hipError_t e = hipGetLastError();
-    scratch_free(block, s);
-    ZG_HIP(e);
+    if (const int e = launch_ok("e")) return e;
     return rc;
 }
 
@@ -862,8 +859,9 @@ int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, 
     const size_t temp_bytes = ((size_t)src->rows + 16) * row_bytes * 2;
     if (n > 1 && ((src_frame | dst_frame) & 15)) return -1;
     const uint32_t per_launch = (uint32_t)std::min<size_t>(std::min(n, MAX_FRAMES_PER_LAUNCH), std::max<size_t>(1, scratch_block_budget() / 2 / temp_bytes));
-    uint32_t *temp = nullptr;
-    if (int rc = scratch_alloc((void **)&temp, temp_bytes * per_launch, s)) return rc;
+    ScratchBlock block(s);
+    if (int rc = block.alloc(temp_bytes * per_launch)) return rc;
+    uint32_t *temp = (uint32_t *)block.p;
     const int tiles_x = (int)ceil_div((uint32_t)row_bytes, 1024u);
     const int rows_per_wave = 4; // 1, 2 and 8 measured the same or worse (profiles/r05_experiments.txt)
     for (uint32_t f0 = 0; f0 < n; f0 += per_launch) {
@@ -915,10 +913,7 @@ int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, 
             else hipLaunchKernelGGL((k_cols_u8f<false, B2_R>), grid2, dim3(256), 0, s, (const uint32_t *)temp, out, dst->stride * sp, (int)src->rows, row_bytes, tc, nky, halfy, border, tiles_x2, fr);
         }
     }
-    const hipError_t e = hipGetLastError();
-    scratch_free(temp, s);
-    ZG_HIP(e);
-    return ZG_OK;
+    return launch_ok("e");
 }
 
 } // namespace zg

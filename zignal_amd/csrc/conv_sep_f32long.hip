@@ -224,9 +224,10 @@ static int run_sep_f32long(const zg_image *src, int grey, size_t sp, const zg_im
     for (int j = 0; j < nky; ++j) tc.k[FL_R + j] = fy[j];
 
     const int row_f = (int)(src->cols * sp);
-    float *temp = nullptr;
+    ScratchBlock block(s);
     // + 16 slack rows: the column pass prefetches up to 15 rows past a strip's last one (never applied)
-    if (int rc = scratch_alloc((void **)&temp, ((size_t)src->rows + 16) * row_f * sizeof(float), s)) return rc;
+    if (int rc = block.alloc(((size_t)src->rows + 16) * row_f * sizeof(float))) return rc;
+    float *temp = (float *)block.p;
     const int tiles_rx = (int)ceil_div((uint32_t)row_f, 256u);
     const int rows_per_wave = 4;
     const dim3 grid_rows((unsigned)(tiles_rx * ceil_div(src->rows, 4u * rows_per_wave)));
@@ -238,10 +239,7 @@ static int run_sep_f32long(const zg_image *src, int grey, size_t sp, const zg_im
     const int tiles_cx = (int)ceil_div((uint32_t)row_f, 1024u);
     hipLaunchKernelGGL(k_cols_f32, dim3((unsigned)(tiles_cx * ceil_div(src->rows, (uint32_t)FL_R))), dim3(256), 0, s, (const float *)temp, (float *)dst->data,
                        dst->stride * sp, (int)src->rows, row_f, tc, nky, halfy, border, tiles_cx);
-    const hipError_t e = hipGetLastError();
-    scratch_free(temp, s);
-    ZG_HIP(e);
-    return ZG_OK;
+    return launch_ok("e");
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the general kernels).

@@ -155,8 +155,7 @@ static int launch_f32x4(const zg_image *src, const zg_image *dst, const float *f
         hipLaunchKernelGGL((k_sep_f32x4<NK, RPT, true>), grid, dim3(256), 0, s, dimg(src), dimg(dst), kx, ky, border, skipx, skipy, tiles_x);
     else
         hipLaunchKernelGGL((k_sep_f32x4<NK, RPT, false>), grid, dim3(256), 0, s, dimg(src), dimg(dst), kx, ky, border, skipx, skipy, tiles_x);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the general kernel).

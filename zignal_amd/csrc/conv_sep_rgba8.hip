@@ -232,8 +232,7 @@ static int launch_rgba8(const Rgba8Batch &b, const int32_t *ix, const int32_t *i
     const DImg dst{b.dst, b.dst_stride, (int32_t)(DOWN2 ? b.rows / 2 : b.rows), (int32_t)(DOWN2 ? b.cols / 2 : b.cols)};
     hipLaunchKernelGGL((k_sep_rgba8<NK, RPT, true, CLAMP, DOWN2>), dim3((unsigned)(tiles_per_frame * b.n_frames)), dim3(256), 0, s,
                        src, dst, b.src_frame_px, b.dst_frame_px, kx, ky, border, tiles_x, tiles_per_frame);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the general kernels).

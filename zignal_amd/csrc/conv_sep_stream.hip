@@ -443,13 +443,11 @@ static int launch_stream(const StreamJob &j, const int32_t *ix, const int32_t *i
     if constexpr (!CLAMP) {
         if (unit) {
             hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, true>), dim3((unsigned)items), dim3(64), 0, s, a, kx, ky);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         }
     }
     hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, false>), dim3((unsigned)items), dim3(64), 0, s, a, kx, ky);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the tiled kernels).

@@ -223,8 +223,7 @@ static int launch_tile_f32(const zg_image *src, const zg_image *dst, uint32_t n,
     const uint64_t items = (uint64_t)a.strips_x * tiles_y;
     if (items > 0x7fffffffu) return -1;
     hipLaunchKernelGGL((k_sep_tile_f32<NK, R, OUTER>), dim3((unsigned)items, n), dim3(64), 0, s, a, kx, ky);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // n <= SF_MAX_PLANES planes of one shape, stride and alignment class in one launch. Returns -1 when the preconditions do not hold

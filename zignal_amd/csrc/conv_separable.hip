@@ -409,8 +409,7 @@ static int launch_fused_v(const zg_image *src, const zg_image *dst, const SepPla
     const int tiles_x = (int)ceil_div(src->cols, TW), tiles_y = (int)ceil_div(src->rows, 4 * RPT);
     hipLaunchKernelGGL((k_sep_fused<PIX, NK, MODE, SKIP, RPT, NT>), dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s,
                        dimg(src), dimg(dst), kx, ky, border, p.skipx, p.skipy, tiles_x);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 template <int PIX, int NK, int MODE, bool SKIP>
@@ -450,21 +449,22 @@ static int launch_two_pass(const zg_image *src, const zg_image *dst, const SepPl
     const size_t temp_bytes = (size_t)src->rows * src->cols * temp_lanes<C>() * sizeof(Temp);
     if (p.nkx > MAX_TAPS || p.nky > MAX_TAPS)
         if (int rc = refuse_under_capture(s, "a separable convolution of more than 255 taps on this route (the taps are uploaded from host memory)")) return rc;
-    Temp *temp = nullptr;
-    if (int rc = scratch_alloc((void **)&temp, temp_bytes, s)) return rc;
+    ScratchBlock temp_block(s), taps_dev(s); // released in the reverse order: the taps before the temp plane
+    if (int rc = temp_block.alloc(temp_bytes)) return rc;
+    Temp *temp = (Temp *)temp_block.p;
     TapsBig tx{}, ty{};
-    void *taps_dev = nullptr; // kernels longer than MAX_TAPS: [kx | ky] in device memory (uploaded synchronously: not capturable)
+    // taps_dev: kernels longer than MAX_TAPS, [kx | ky] in device memory (uploaded synchronously: not capturable)
     const void *mx = nullptr, *my = nullptr;
     if (p.nkx > MAX_TAPS || p.nky > MAX_TAPS) {
         const size_t n = (size_t)p.nkx + (size_t)p.nky;
         std::vector<uint32_t> host(n);
         if constexpr (MODE == MODE_F32) { std::memcpy(host.data(), p.fx.data(), (size_t)p.nkx * 4); std::memcpy(host.data() + p.nkx, p.fy.data(), (size_t)p.nky * 4); }
         else { std::memcpy(host.data(), p.ix.data(), (size_t)p.nkx * 4); std::memcpy(host.data() + p.nkx, p.iy.data(), (size_t)p.nky * 4); }
-        int rc = scratch_alloc(&taps_dev, n * 4, s);
-        if (rc == ZG_OK) rc = upload_pageable(taps_dev, host.data(), n * 4, s);
-        if (rc) { scratch_free(taps_dev, s); scratch_free(temp, s); return rc; }
-        mx = taps_dev;
-        my = (const uint32_t *)taps_dev + p.nkx;
+        int rc = taps_dev.alloc(n * 4);
+        if (rc == ZG_OK) rc = upload_pageable(taps_dev.p, host.data(), n * 4, s);
+        if (rc) return rc;
+        mx = taps_dev.p;
+        my = (const uint32_t *)taps_dev.p + p.nkx;
     } else {
         for (int i = 0; i < p.nkx; ++i) { if constexpr (MODE == MODE_F32) tx.f[i] = p.fx[i]; else tx.i[i] = p.ix[i]; }
         for (int i = 0; i < p.nky; ++i) { if constexpr (MODE == MODE_F32) ty.f[i] = p.fy[i]; else ty.i[i] = p.iy[i]; }
@@ -472,12 +472,7 @@ static int launch_two_pass(const zg_image *src, const zg_image *dst, const SepPl
     const dim3 grid = row_grid(ceil_div(src->cols, 256), src->rows);
     hipLaunchKernelGGL((k_sep_h<PIX, MODE>), grid, dim3(256), 0, s, dimg(src), temp, tx, mx, p.nkx, border);
     hipLaunchKernelGGL((k_sep_v<PIX, MODE>), grid, dim3(256), 0, s, temp, dimg(dst), ty, my, p.nky, border);
-    const hipError_t launch_error = hipGetLastError();
-    scratch_free(taps_dev, s);
-    if (launch_error != hipSuccess) { scratch_free(temp, s); ZG_HIP(launch_error); }
-    ZG_HIP(hipGetLastError());
-    scratch_free(temp, s);
-    return ZG_OK;
+    return launch_ok("launch_error");
 }
 
 template <int PIX, int MODE>

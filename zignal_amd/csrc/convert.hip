@@ -250,8 +250,7 @@ static int launch_lab4(const zg_image *src, const zg_image *dst, int dst_space, 
     if (four) { if (mode == 0) ZG_LAB4(4, 0); else if (mode == 1) ZG_LAB4(4, 1); else if (mode == 2) ZG_LAB4(4, 2); else if (mode == 3) ZG_LAB4(4, 3); else ZG_LAB4(4, 4); }
     else { if (mode == 0) ZG_LAB4(3, 0); else if (mode == 1) ZG_LAB4(3, 1); else if (mode == 2) ZG_LAB4(3, 2); else if (mode == 3) ZG_LAB4(3, 3); else ZG_LAB4(3, 4); }
 #undef ZG_LAB4
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // The way back, Lab(f32) -> Rgb(u8) / Rgba(u8) (route Lab -> Xyz -> Rgb -> u8, colorspaces.hip's hops: color.zig:1311-1330, :1275-1286, then
@@ -329,14 +328,12 @@ static int launch_lab4_back(const zg_image *src, const zg_image *dst, hipStream_
         hipLaunchKernelGGL(k_lab4_to_u8<4>, grid, dim3(256), 0, s, (const uint8_t *)src->data, (uint8_t *)dst->data, spitch, (uint64_t)dst->stride * 4, (int)src->rows, (int)src->cols);
     else
         hipLaunchKernelGGL(k_lab4_to_u8<3>, grid, dim3(256), 0, s, (const uint8_t *)src->data, (uint8_t *)dst->data, spitch, (uint64_t)dst->stride * 3, (int)src->rows, (int)src->cols);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // `plain` (optional) comes back true when every entry of the table is +0 or a positive number within [2^-60, 2^60]: what
 // xyz_to_oklab<true> asks for. The library's own sRGB table is (entry 1 is 3.0e-4).
-static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **out, float **owned, bool *plain = nullptr) {
-    *owned = nullptr;
+static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **out, ScratchBlock *owned, bool *plain = nullptr) {
     if (plain) {
         *plain = true;
         if (host_lut)
@@ -348,9 +345,9 @@ static int device_srgb_lut(const float *host_lut, hipStream_t s, const float **o
     }
     if (host_lut) {
         if (int rc = refuse_under_capture(s, "a caller's sRGB table (srgb_lut, uploaded from host memory)")) return rc;
-        if (int rc = scratch_alloc((void **)owned, 256 * sizeof(float), s)) return rc;
-        if (int rc = upload_pageable(*owned, host_lut, 256 * sizeof(float), s)) return rc;
-        *out = *owned;
+        if (int rc = owned->alloc(256 * sizeof(float))) return rc;
+        if (int rc = upload_pageable(owned->p, host_lut, 256 * sizeof(float), s)) return rc;
+        *out = (const float *)owned->p;
         return ZG_OK;
     }
     static std::mutex mu;
@@ -400,17 +397,12 @@ int convert_impl(const zg_image *src, int src_space, const zg_image *dst, int ds
         if (src_space == dst_space && src->pixel == dst->pixel) return copy_impl(src, dst, s);
         if (lab4_back_applies(src, dst, src_space, dst_space)) return launch_lab4_back(src, dst, s); // Lab(f32) -> Rgb(u8) / Rgba(u8), four pixels per lane
         const float *lut_dev = nullptr; // gammaToLinear(u8 / 255): the caller's table if given, else the library's
-        float *lut_owned = nullptr;
+        ScratchBlock lut_owned(s);
         bool plain_lut = false;
         if (!sf && (rc = device_srgb_lut(srgb_lut, s, &lut_dev, &lut_owned, &plain_lut))) return rc;
-        if (lab4_applies(src, dst, src_space, dst_space)) { // Rgb(u8) / Rgba(u8) -> Lab(f32): the route Rgb -> Xyz -> Lab, four pixels per lane
-            rc = launch_lab4(src, dst, dst_space, lut_dev, plain_lut, s);
-            if (lut_owned) scratch_free(lut_owned, s);
-            return rc;
-        }
-        rc = convert_spaces_impl(src, src_space, dst, dst_space, lut_dev, s);
-        if (lut_owned) scratch_free(lut_owned, s);
-        return rc;
+        // Rgb(u8) / Rgba(u8) -> Lab(f32): the route Rgb -> Xyz -> Lab, four pixels per lane
+        if (lab4_applies(src, dst, src_space, dst_space)) return launch_lab4(src, dst, dst_space, lut_dev, plain_lut, s);
+        return convert_spaces_impl(src, src_space, dst, dst_space, lut_dev, s);
     }
     if (dst_space == ZG_CS_XYZ || dst_space == ZG_CS_OKLAB) ZG_REQUIRE(df, ZG_ERR_UNSUPPORTED, "convert: Xyz / Oklab need a float destination");
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
@@ -419,32 +411,24 @@ int convert_impl(const zg_image *src, int src_space, const zg_image *dst, int ds
     if (src->pixel == ZG_PIXEL_U8 && dst->pixel == ZG_PIXEL_RGBA_U8 && src_space == ZG_CS_GRAY && dst_space == ZG_CS_RGBA && src->cols % 4 == 0 && src->stride % 4 == 0 &&
         dst->stride % 4 == 0 && ((uintptr_t)src->data & 3) == 0 && ((uintptr_t)dst->data & 15) == 0) {
         hipLaunchKernelGGL(k_gray8_to_rgba8_4, row_grid(ceil_div(src->cols, 1024), src->rows), dim3(256), 0, s, dimg(src), dimg(dst));
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     }
     ConvertArgs a{src_space, dst_space, nullptr};
-    float *owned = nullptr;
+    ScratchBlock owned(s);
     bool plain_table = false;
     if (!sf && (dst_space == ZG_CS_XYZ || dst_space == ZG_CS_OKLAB)) {
         if ((rc = device_srgb_lut(srgb_lut, s, &a.srgb_lut, &owned, &plain_table))) return rc;
     }
-    if (lab4_applies(src, dst, src_space, dst_space)) {
-        rc = launch_lab4(src, dst, dst_space, a.srgb_lut, plain_table, s);
-        if (owned) scratch_free(owned, s);
-        return rc;
-    }
+    if (lab4_applies(src, dst, src_space, dst_space)) return launch_lab4(src, dst, dst_space, a.srgb_lut, plain_table, s);
     const dim3 grid = row_grid(ceil_div(src->cols, 256), src->rows);
-    rc = dispatch_pixel(src->pixel, [&](auto stag) -> int {
+    return dispatch_pixel(src->pixel, [&](auto stag) -> int {
         constexpr int SPIX = decltype(stag)::value;
         return dispatch_pixel(dst->pixel, [&](auto dtag) -> int {
             constexpr int DPIX = decltype(dtag)::value;
             hipLaunchKernelGGL((k_convert<SPIX, DPIX>), grid, dim3(256), 0, s, dimg(src), dimg(dst), a);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         });
     });
-    if (owned) scratch_free(owned, s);
-    return rc;
 }
 
 
@@ -532,7 +516,7 @@ int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int ds
     if (tiles > 0x7fffffffu || n > MAX_FRAMES_PER_LAUNCH) return -1;
     const dim3 grid((unsigned)tiles, n);
     const float *lut_dev = nullptr;
-    float *owned = nullptr;
+    ScratchBlock owned(s);
     bool plain_table = false;
     if (int rc = device_srgb_lut(srgb_lut, s, &lut_dev, &owned, &plain_table)) return rc;
     const float ratio_x = (float)src->cols / (float)dst->cols, ratio_y = (float)src->rows / (float)dst->rows;
@@ -545,10 +529,7 @@ int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int ds
     }
     ZG_RL(0) ZG_RL(1) ZG_RL(2)
 #undef ZG_RL
-    const hipError_t e = hipGetLastError();
-    if (owned) scratch_free(owned, s);
-    ZG_HIP(e);
-    return ZG_OK;
+    return launch_ok("e");
 }
 
 static int resize_convert_impl(const zg_image *src, int src_space, const zg_image *dst, int dst_space, const zg_method *method,
@@ -567,12 +548,11 @@ static int resize_convert_impl(const zg_image *src, int src_space, const zg_imag
     mid.rows = dst->rows;
     mid.cols = dst->cols;
     mid.stride = dst->cols;
-    mid.data = nullptr;
-    if ((rc = scratch_alloc(&mid.data, (size_t)mid.rows * mid.cols * pixel_size(mid.pixel), s))) return rc;
-    rc = resize_impl(src, &mid, method, s);
-    if (rc == ZG_OK) rc = convert_impl(&mid, src_space, dst, dst_space, srgb_lut, s);
-    scratch_free(mid.data, s);
-    return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc((size_t)mid.rows * mid.cols * pixel_size(mid.pixel)))) return rc;
+    mid.data = block.p;
+    if ((rc = resize_impl(src, &mid, method, s))) return rc;
+    return convert_impl(&mid, src_space, dst, dst_space, srgb_lut, s);
 }
 
 
@@ -641,8 +621,7 @@ int zg_devmath_apply(int fn, const float *x_dev, const float *y_dev, float *out_
     if (n == 0) return ZG_OK;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(k_devmath_apply, dim3(blocks), dim3(256), 0, as_stream(stream), fn, x_dev, y_dev, out_dev, n);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 

@@ -107,8 +107,7 @@ static int sobel_impl(const zg_image *src, const zg_image *dst, hipStream_t s, u
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         hipLaunchKernelGGL((k_sobel<PIX>), dim3((unsigned)(tiles_x * tiles_y), n), dim3(256), 0, s, dimg(src), dimg(dst), tiles_x, fr);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
 }
 // Image.sobel of n equally shaped frames in one launch (-1: too many frames for one grid)
@@ -532,7 +531,7 @@ static int run_hysteresis(uint8_t *state, uint32_t rows, uint32_t cols, char *wo
         hipLaunchKernelGGL(k_cc_border, dim3(ceil_div(rows > cols ? rows : cols, 256u), nvb + nhb), dim3(256), 0, s, (const uint8_t *)state, label, (int)rows, (int)cols, (int)nvb);
     hipLaunchKernelGGL(k_cc_mark, dim3(nb), dim3(256), 0, s, (const uint8_t *)state, label, flag, n);
     hipLaunchKernelGGL(k_cc_emit_tile, tiles, dim3(256), 0, s, (const uint8_t *)state, label, (const uint16_t *)label16, (const uint8_t *)flag, dimg(dst), (int)rows, (int)cols);
-    if (hipGetLastError() != hipSuccess) { set_error("%s: hysteresis launch failed", who); return ZG_ERR_HIP; }
+    if (launch_ok("hysteresis")) { set_error("%s: hysteresis launch failed", who); return ZG_ERR_HIP; }
     return ZG_OK;
 }
 static size_t hysteresis_work_bytes(uint32_t rows, uint32_t cols) {
@@ -572,7 +571,7 @@ static int launch_emit(const uint8_t *state, int *label, const uint8_t *flag, co
     const bool vec = dst->cols % 4 == 0 && dst->stride % 4 == 0 && (uintptr_t)dst->data % 4 == 0;
     if (vec) hipLaunchKernelGGL(k_canny_emit<true>, grid, dim3(256), 0, s, state, label, flag, dimg(dst));
     else hipLaunchKernelGGL(k_canny_emit<false>, grid, dim3(256), 0, s, state, label, flag, dimg(dst));
-    return hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
+    return launch_ok("k_canny_emit");
 }
 
 static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, float low, float high, zg_stream stream) {
@@ -592,12 +591,13 @@ static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, flo
     ZG_REQUIRE(n <= 0x7fffffffu, ZG_ERR_UNSUPPORTED, "canny: hysteresis labels are 32-bit (rows * cols must stay below 2^31)");
 
     // scratch: grey f32 | blurred f32 | state u8 | hysteresis work
-    char *scratch = nullptr;
-    const size_t state_off = 2 * n * sizeof(float), work_off = (state_off + n + 255) / 256 * 256;
-    if ((rc = scratch_alloc((void **)&scratch, work_off + hysteresis_work_bytes(rows, cols), s))) return rc;
-    float *gray = (float *)scratch, *blur = gray + n;
-    uint8_t *state = (uint8_t *)(scratch + state_off);
-    char *work = scratch + work_off;
+    ScratchBlock scratch(s);
+    char *planes, *work;
+    scratch.take(planes, 2 * n * sizeof(float) + n);
+    scratch.take(work, hysteresis_work_bytes(rows, cols));
+    if ((rc = scratch.alloc())) return rc;
+    float *gray = (float *)planes, *blur = gray + n;
+    uint8_t *state = (uint8_t *)(blur + n);
 
     const float *blurred = gray;
     bool have_gray = false;
@@ -606,15 +606,14 @@ static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, flo
         return dispatch_pixel(src->pixel, [&](auto tag) -> int {
             constexpr int PIX = decltype(tag)::value;
             launch_canny_gray<PIX>(src, gray, s);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+            return launch_ok();
         });
     };
     if (sigma == 0) rc = make_gray();
     if (rc == ZG_OK && sigma != 0) { // blurGaussian (edges.zig:663-687): its own taps, .replicate
         const size_t radius = (size_t)std::ceil(3.0f * sigma), ks = 2 * radius + 1;
         // any length the separable convolution takes (kernels past 255 taps are read from device memory); the reference has no limit
-        if (!(3.0f * sigma < 2000000.0f)) { scratch_free(scratch, s); ZG_REQUIRE(false, ZG_ERR_INVALID_ARGUMENT, "canny: sigma %g is out of range", (double)sigma); }
+        ZG_REQUIRE(3.0f * sigma < 2000000.0f, ZG_ERR_INVALID_ARGUMENT, "canny: sigma %g is out of range", (double)sigma);
         std::vector<float> k(ks);
         float sum = 0;
         for (size_t i = 0; i < ks; ++i) {
@@ -637,7 +636,6 @@ static int canny_impl(const zg_image *src, const zg_image *dst, float sigma, flo
         hipLaunchKernelGGL(k_canny_nms, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, blurred, state, (int)rows, (int)cols, low, high, tiles_x);
         rc = run_hysteresis(state, rows, cols, work, dst, s, "canny");
     }
-    scratch_free(scratch, s);
     return rc;
 }
 
@@ -1193,11 +1191,12 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
 
     // scratch: f32 planes grey | smoothed | temp (ISEF) then grey*BLI | gradient | three SATs; u8 planes BLI | candidates | NMS | state;
     // histogram (256) | thresholds (2) | hysteresis work
-    char *scratch = nullptr;
+    ScratchBlock block(s);
     const size_t f32_bytes = 7 * nf * sizeof(float), u8_off = f32_bytes, small_off = (u8_off + 6 * nf + 255) / 256 * 256;
     constexpr size_t small_bytes = SC_HIST_COPIES * 256 * sizeof(unsigned int) + 256; // histogram copies | thresholds
     const size_t check_off = (small_off + small_bytes + hysteresis_work_bytes(rows, cols) + 255) / 256 * 256; // the segmented ISEF's check words
-    if ((rc = scratch_alloc((void **)&scratch, check_off + isef_check_bytes(rows, cols), s))) return rc;
+    if ((rc = block.alloc(check_off + isef_check_bytes(rows, cols)))) return rc;
+    char *scratch = block.p;
     float *gray = (float *)scratch, *sm = gray + nf, *temp = sm + nf, *grad = temp + nf, *sat_g = grad + nf, *sat_m = sat_g + nf, *sat_gm = sat_m + nf;
     uint8_t *bli = (uint8_t *)(scratch + u8_off), *cand = bli + nf, *nms = cand + nf, *state = nms + nf, *gray8 = state + nf, *gm8 = gray8 + nf;
     unsigned int *hist = (unsigned int *)(scratch + small_off);
@@ -1211,8 +1210,7 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
     rc = dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         launch_canny_gray<PIX>(src, gray_f32 ? gray : nullptr, s, bytes ? gray8 : nullptr);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
     const dim3 g64(ceil_div(cols, 64), ceil_div(rows, 4));
     if (rc == ZG_OK) {
@@ -1230,7 +1228,7 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
         } else {
             hipLaunchKernelGGL(k_sc_bli, g64, dim3(256), 0, s, (const float *)gray, (const float *)sm, bli, temp /* grey * BLI */, cand, (int)rows, (int)cols, use_nms ? 0 : 1);
         }
-        if (hipGetLastError() != hipSuccess) rc = ZG_ERR_HIP;
+        rc = launch_ok("k_sc_bli");
     }
     // frames of at most 2^24 pixels, windows up to 15 x 15: the mask's window count is exact in the reference's f32 integral image, so it is
     // counted directly (k_sc_count) and only grey and grey * BLI go through integral images
@@ -1276,10 +1274,9 @@ static int shen_castan_impl(const zg_image *src, const zg_image *dst, float smoo
             final_cand = nms;
         }
         hipLaunchKernelGGL(k_sc_classify4, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, final_cand, (const float *)grad, (const float *)thr, state, n, hysteresis ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) rc = ZG_ERR_HIP;
+        if (const int e = launch_ok("k_sc_classify4")) rc = e; // a failed fill_async above stays reported
     }
     if (rc == ZG_OK) rc = hysteresis ? run_hysteresis(state, rows, cols, work, dst, s, "shenCastan") : launch_emit(state, nullptr, nullptr, dst, s);
-    scratch_free(scratch, s);
     return rc;
 }
 
@@ -1313,9 +1310,9 @@ int zg_isef_smooth(const zg_image *src, const zg_image *dst, float smooth, zg_st
     hipStream_t s = as_stream(stream);
     const uint32_t rows = src->rows, cols = src->cols;
     const size_t nf = ((size_t)rows * cols + 3) / 4 * 4;
-    char *scratch = nullptr;
-    if (const int rc = scratch_alloc((void **)&scratch, 4 * nf * sizeof(float) + isef_check_bytes(rows, cols), s)) return rc;
-    float *tmp = (float *)scratch, *t1 = tmp + nf, *t2 = t1 + nf, *as_f32 = t2 + nf;
+    ScratchBlock scratch(s);
+    if (const int rc = scratch.alloc(4 * nf * sizeof(float) + isef_check_bytes(rows, cols))) return rc;
+    float *tmp = (float *)scratch.p, *t1 = tmp + nf, *t2 = t1 + nf, *as_f32 = t2 + nf;
     const float *gray = (const float *)src->data;
     const uint8_t *gray8 = nullptr;
     if (src->pixel == ZG_PIXEL_U8) { // as the detector has it: bytes for the segmented row pass, f32 only where that does not apply
@@ -1330,10 +1327,7 @@ int zg_isef_smooth(const zg_image *src, const zg_image *dst, float smooth, zg_st
         }
     }
     isef_plane(gray, gray8, (float *)dst->data, tmp, t1, t2, (uint32_t *)(as_f32 + nf), rows, cols, smooth, s);
-    const hipError_t e = hipGetLastError();
-    scratch_free(scratch, s);
-    ZG_HIP(e);
-    return ZG_OK;
+    return launch_ok("e");
 }
 
 int zg_shen_castan(const zg_image *src, const zg_image *dst, float smooth, uint32_t window_size, float high_ratio, float low_rel, int hysteresis,
@@ -1381,13 +1375,11 @@ int zg_pyramid_build_level(const zg_image *source, const zg_image *level, float 
             }
         }
     }
-    void *blurred = nullptr;
-    if ((rc = scratch_alloc(&blurred, (size_t)source->rows * source->cols * pixel_size(source->pixel), s))) return rc;
-    const zg_image tmp{blurred, source->cols, source->rows, source->cols, source->pixel};
-    rc = zg_gaussian_blur(source, &tmp, sigma, stream);
-    if (rc == ZG_OK) rc = zg_resize(&tmp, level, &bilinear, stream);
-    scratch_free(blurred, s);
-    return rc;
+    ScratchBlock blurred(s);
+    if ((rc = blurred.alloc((size_t)source->rows * source->cols * pixel_size(source->pixel)))) return rc;
+    const zg_image tmp{blurred.p, source->cols, source->rows, source->cols, source->pixel};
+    if ((rc = zg_gaussian_blur(source, &tmp, sigma, stream))) return rc;
+    return zg_resize(&tmp, level, &bilinear, stream);
 }
 
 // ImagePyramid.build (pyramid.zig:31-102) as one device operation: every level is made from the ORIGINAL (blur with its own sigma, then

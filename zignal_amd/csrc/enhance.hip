@@ -98,23 +98,23 @@ static int enhance_impl(const zg_image *img, bool equalize, float cutoff, hipStr
     ZG_REQUIRE(total <= 0xffffffffu / 255u, ZG_ERR_UNSUPPORTED, "autocontrast / equalize: %zu pixels overflow the reference's u32 arithmetic", total);
     const unsigned int cutoff_pixels = equalize ? 0u : (unsigned int)std::trunc((float)total * cutoff);
     const int nch = pixel_channels(img->pixel), nlut = equalize ? nch : (nch == 4 ? 3 : nch);
-    char *scratch = nullptr;
-    if ((rc = scratch_alloc((void **)&scratch, 4 * 256 * sizeof(unsigned int) + 4 * 256, s))) return rc;
-    unsigned int *hist = (unsigned int *)scratch;
-    uint8_t *lut = (uint8_t *)(hist + 4 * 256);
-    if ((rc = fill_async(hist, 0, 4 * 256 * sizeof(unsigned int), s))) { scratch_free(scratch, s); return rc; }
-    rc = dispatch_pixel(img->pixel, [&](auto tag) -> int {
+    ScratchBlock scratch(s); // [histograms][tables]
+    unsigned int *hist;
+    uint8_t *lut;
+    scratch.take(hist, 4 * 256);
+    scratch.take(lut, 4 * 256);
+    if ((rc = scratch.alloc())) return rc;
+    if ((rc = fill_async(hist, 0, 4 * 256 * sizeof(unsigned int), s))) return rc;
+    return dispatch_pixel(img->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         if constexpr (!std::is_same<typename Px<PIX>::Elem, float>::value) {
             hipLaunchKernelGGL((k_hist_channels<PIX>), dim3(ceil_div(img->cols, 64), ceil_div(img->rows, 64)), dim3(256), 0, s, dimg(img), hist);
             hipLaunchKernelGGL(k_enhance_luts, dim3(1), dim3(256), 0, s, (const unsigned int *)hist, lut, nch, nlut, equalize ? 1 : 0, cutoff_pixels, (unsigned int)total);
             hipLaunchKernelGGL((k_apply_luts<PIX>), dim3(ceil_div(img->cols, 256), img->rows), dim3(256), 0, s, dimg(img), (const uint8_t *)lut);
-            ZG_HIP(hipGetLastError());
+            if (const int e = launch_ok()) return e;
         }
         return ZG_OK;
     });
-    scratch_free(scratch, s);
-    return rc;
 }
 
 } // namespace zg

@@ -20,6 +20,7 @@
 // A batch of images (a pyramid's levels) runs the same three launches: a job table in the kernel arguments, workgroups of all
 // jobs in one grid, each finding its job from the per-stage first-workgroup table.
 #include "zg_internal.h"
+#include "zg_scan.h"
 
 #include <algorithm>
 #include <vector>
@@ -344,46 +345,29 @@ __global__ __launch_bounds__(256) void k_fast_row_write(FastBatch b) {
     const FastJob &J = b.job[j];
     const uint32_t y = blockIdx.x - b.first[j];
     const uint16_t *row = J.score + (size_t)y * J.iw;
-    __shared__ uint32_t wave_n[4];
     __shared__ uint32_t acc;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     if (y == 0) write_total(J, &acc); // uniform
     if (J.counts[y] == 0) return;
     uint32_t base = cell_offset(J, y, &acc);
     for (int x0 = 0; x0 < J.iw && base < J.capacity; x0 += 256) {
         const int x = x0 + tid;
         const int s = x < J.iw ? row[x] : 0;
-        const uint64_t ballot = __ballot(s != 0);
-        if (lane == 0) wave_n[w] = (uint32_t)__popcll(ballot);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (int i = 0; i < 4; ++i) {
-            before += i < w ? wave_n[i] : 0u;
-            total += wave_n[i];
-        }
-        before += (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+        uint32_t total;
+        const uint32_t before = block_exclusive_count(s != 0, &total);
         if (s) write_keypoint(J, base + before, (int)y + 3, x + 3, s);
         base += total;
-        __syncthreads(); // wave_n is rewritten by the next chunk
     }
 }
 
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return ZG_OK;
-}
-
-int check_fast_image(const zg_image *im, const char *name) {
+int check_fast_image(const zg_image *im, const char *name, bool device_pointer = true) {
     int rc;
-    if ((rc = check_image(im, name))) return rc;
+    if ((rc = check_image(im, name, device_pointer))) return rc;
     ZG_REQUIRE(im->pixel == ZG_PIXEL_U8, ZG_ERR_UNSUPPORTED, "fast: %s is not Image(u8) (Fast.detect takes Image(u8) only)", name);
     ZG_REQUIRE(im->rows > 7 && im->cols > 7, ZG_ERR_INVALID_ARGUMENT, "fast: %s is %ux%u; Fast.detect needs rows > 7 and cols > 7 (Fast.zig:39)",
                name, im->rows, im->cols);
     return ZG_OK;
 }
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // n independent Fast.detect calls (validated), scratch from the caching allocator, three launches per group of FAST_MAX_JOBS.
 int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t min_contiguous, int nms, zg_keypoint *const *outs,
@@ -392,9 +376,8 @@ int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uin
     std::vector<FastJob> jobs(n);
     // scratch: the minrc words of every job (set to 0xFF), the group totals of every job (zeroed), then per job its score map
     // and cell counts
-    const size_t minrc_bytes = align256((size_t)n * 2 * sizeof(uint32_t));
     size_t gtot_words = 0;
-    std::vector<size_t> off(n), goff(n);
+    std::vector<size_t> goff(n);
     for (uint32_t i = 0; i < n; ++i) {
         const zg_image &im = images[i];
         FastJob &J = jobs[i];
@@ -418,25 +401,22 @@ int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uin
         goff[i] = gtot_words;
         gtot_words += (size_t)J.ngroups;
     }
-    const size_t gtot_bytes = align256(gtot_words * sizeof(uint32_t));
-    size_t bytes = minrc_bytes + gtot_bytes;
-    for (uint32_t i = 0; i < n; ++i) {
-        const FastJob &J = jobs[i];
-        off[i] = bytes;
-        bytes += align256((size_t)J.ih * J.iw * sizeof(uint16_t)) + align256((size_t)J.cells_x * J.cells_y * sizeof(uint32_t));
+    ScratchBlock sc(s);
+    uint32_t *minrc, *gtot;
+    sc.take(minrc, (size_t)n * 2);
+    sc.take(gtot, gtot_words);
+    for (FastJob &J : jobs) {
+        sc.take(J.score, (size_t)J.ih * J.iw);
+        sc.take(J.counts, (size_t)J.cells_x * J.cells_y);
     }
-    char *scratch = nullptr;
     int rc;
-    if ((rc = scratch_alloc((void **)&scratch, bytes, s))) return rc;
+    if ((rc = sc.alloc())) return rc;
     for (uint32_t i = 0; i < n; ++i) {
-        FastJob &J = jobs[i];
-        J.minrc = (uint32_t *)scratch + 2 * i;
-        J.gtot = (uint32_t *)(scratch + minrc_bytes) + goff[i];
-        J.score = (uint16_t *)(scratch + off[i]);
-        J.counts = (uint32_t *)(scratch + off[i] + align256((size_t)J.ih * J.iw * sizeof(uint16_t)));
+        jobs[i].minrc = minrc + 2 * i;
+        jobs[i].gtot = gtot + goff[i];
     }
-    rc = fill_async(scratch + minrc_bytes, 0, gtot_words * sizeof(uint32_t), s);
-    if (rc == ZG_OK && nms) rc = fill_async(scratch, 0xFF, (size_t)n * 2 * sizeof(uint32_t), s);
+    rc = fill_async(gtot, 0, gtot_words * sizeof(uint32_t), s);
+    if (rc == ZG_OK && nms) rc = fill_async(minrc, 0xFF, (size_t)n * 2 * sizeof(uint32_t), s);
     for (uint32_t g = 0; g < n && rc == ZG_OK; g += FAST_MAX_JOBS) {
         FastBatch b{};
         b.n = (int32_t)std::min<uint32_t>(FAST_MAX_JOBS, n - g);
@@ -458,7 +438,6 @@ int fast_run(const zg_image *images, uint32_t n, const uint32_t *thresholds, uin
         else hipLaunchKernelGGL(k_fast_row_write, dim3(cells), dim3(256), 0, s, b);
         rc = launch_ok("k_fast_write");
     }
-    scratch_free(scratch, s);
     return rc;
 }
 
@@ -495,25 +474,21 @@ int zg_fast_detect(const zg_image *src, uint32_t threshold, uint32_t min_contigu
 int zg_fast_detect_host(const zg_image *src, uint32_t threshold, uint32_t min_contiguous, int nonmax_suppression, zg_keypoint *keypoints, uint32_t capacity,
                         uint32_t *count) {
     int rc;
-    if ((rc = check_fast_options(threshold, min_contiguous))) return rc;
-    if ((rc = check_image(src, "src", false))) return rc;
-    ZG_REQUIRE(src->pixel == ZG_PIXEL_U8, ZG_ERR_UNSUPPORTED, "fast: src is not Image(u8) (Fast.detect takes Image(u8) only)");
-    ZG_REQUIRE(src->rows > 7 && src->cols > 7, ZG_ERR_INVALID_ARGUMENT, "fast: src is %ux%u; Fast.detect needs rows > 7 and cols > 7 (Fast.zig:39)",
-               src->rows, src->cols);
+    if ((rc = check_fast_options(threshold, min_contiguous)) || (rc = check_fast_image(src, "src", false))) return rc;
     ZG_REQUIRE(count != nullptr, ZG_ERR_INVALID_ARGUMENT, "fast: null count");
     ZG_REQUIRE(keypoints != nullptr || capacity == 0, ZG_ERR_INVALID_ARGUMENT, "fast: null keypoints with capacity %u", capacity);
     HostStage a;
     if ((rc = a.upload(src, true, false))) return rc;
-    const size_t kp_bytes = align256((size_t)capacity * sizeof(zg_keypoint));
-    char *dev = nullptr;
-    if ((rc = scratch_alloc((void **)&dev, kp_bytes + sizeof(uint32_t), nullptr))) return rc;
-    zg_keypoint *dkp = capacity ? (zg_keypoint *)dev : nullptr;
-    uint32_t *dcount = (uint32_t *)(dev + kp_bytes);
-    rc = fast_run(&a.dev, 1, &threshold, min_contiguous, nonmax_suppression != 0, &dkp, &capacity, &dcount, nullptr);
-    if (rc == ZG_OK) rc = download_pageable(count, dcount, sizeof(uint32_t), nullptr);
-    if (rc == ZG_OK && capacity && *count) rc = download_pageable(keypoints, dkp, (size_t)std::min(*count, capacity) * sizeof(zg_keypoint), nullptr);
-    scratch_free(dev, nullptr);
-    return rc;
+    // scratch: [keypoints][count]
+    ScratchBlock sc;
+    zg_keypoint *dkp;
+    uint32_t *dcount;
+    sc.take(dkp, capacity);
+    sc.take(dcount, 1);
+    if ((rc = sc.alloc())) return rc;
+    if (!capacity) dkp = nullptr;
+    if ((rc = fast_run(&a.dev, 1, &threshold, min_contiguous, nonmax_suppression != 0, &dkp, &capacity, &dcount, nullptr))) return rc;
+    return download_counted(count, dcount, 1, keypoints, dkp, capacity);
 }
 
 int zg_fast_detect_batch(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t min_contiguous, int nonmax_suppression,

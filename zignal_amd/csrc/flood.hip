@@ -252,20 +252,6 @@ template <int PIX> __global__ __launch_bounds__(256) void k_flood_fill(FloodArgs
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return ZG_OK;
-}
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Scratch {
-    char *p = nullptr;
-    hipStream_t s;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() { if (p) scratch_free(p, s); }
-};
-
 bool have_device() { // asked once per process
     static const bool ok = [] {
         int n = 0;
@@ -334,10 +320,11 @@ int flood(const zg_image *img, uint32_t row, uint32_t col, const uint32_t *seed_
     if (count && (rc = fill_async(count, 0, sizeof(uint32_t), s))) return rc;
     const size_t n = (size_t)img->rows * img->cols;
     if (n == 0) return ZG_OK; // only a device seed gets here: it is outside
-    Scratch sc(s);
-    const size_t links_b = align256(n);
-    if ((rc = scratch_alloc((void **)&sc.p, links_b + n * sizeof(int), s))) return rc;
     FloodArgs a{};
+    ScratchBlock sc(s); // scratch: [links][labels]
+    sc.take(a.links, n);
+    sc.take(a.label, n);
+    if ((rc = sc.alloc())) return rc;
     a.data = img->data;
     a.stride = img->stride;
     a.rows = (int)img->rows;
@@ -350,8 +337,6 @@ int flood(const zg_image *img, uint32_t row, uint32_t col, const uint32_t *seed_
     a.bound_i = pixel_is_float(img->pixel) ? -1 : (int)b;
     a.eight = opt->connectivity == 8;
     a.mode = opt->mode;
-    a.links = (uint8_t *)sc.p;
-    a.label = (int *)(sc.p + links_b);
     a.count = count;
     std::memcpy(a.fill, fill_value, pixel_size(img->pixel));
     const unsigned pixel_blocks = (unsigned)((n + 255) / 256);
@@ -408,8 +393,8 @@ int zg_flood_fill_host(const zg_image *img, uint32_t row, uint32_t col, const vo
     if ((rc = check(img, row, col, false, fill_value, opt, false))) return rc;
     HostStage st;
     if ((rc = st.upload(img, true, true))) return rc;
-    Scratch sc(nullptr);
-    if ((rc = scratch_alloc((void **)&sc.p, 256, nullptr))) return rc;
+    ScratchBlock sc;
+    if ((rc = sc.alloc(256))) return rc;
     if ((rc = flood(&st.dev, row, col, nullptr, fill_value, opt, (uint32_t *)sc.p, nullptr))) return rc;
     uint32_t n = 0;
     if ((rc = download_pageable(&n, sc.p, sizeof n, nullptr))) return rc; // waits for the stream

@@ -114,15 +114,16 @@ __global__ __launch_bounds__(256) void k_geom(DImg src, DImg dst, GeomParams g, 
 // ---- Lanczos table on the device ---------------------------------------------------------------
 struct LutHolder {
     const float *dev = nullptr;   // what the kernel reads
-    float *owned = nullptr;       // per-call upload of a caller-supplied table (freed on the stream)
+    ScratchBlock owned;           // per-call upload of a caller-supplied table (freed on the stream)
+    explicit LutHolder(hipStream_t s) : owned(s) {}
 };
 static int device_lanczos_lut(const zg_method *method, hipStream_t s, LutHolder &h) {
     if (method->kind != ZG_INTERP_LANCZOS) return ZG_OK;
     if (method->lanczos_lut) {
         if (int rc = refuse_under_capture(s, "a caller's Lanczos table (zg_method.lanczos_lut, uploaded from host memory)")) return rc;
-        if (int rc = scratch_alloc((void **)&h.owned, 1025 * sizeof(float), s)) return rc;
-        if (int rc = upload_pageable(h.owned, method->lanczos_lut, 1025 * sizeof(float), s)) return rc; // the caller's table may be pageable / short-lived
-        h.dev = h.owned;
+        if (int rc = h.owned.alloc(1025 * sizeof(float))) return rc;
+        if (int rc = upload_pageable(h.owned.p, method->lanczos_lut, 1025 * sizeof(float), s)) return rc; // the caller's table may be pageable / short-lived
+        h.dev = (const float *)h.owned.p;
         return ZG_OK;
     }
     static std::mutex mu;
@@ -139,10 +140,6 @@ static int device_lanczos_lut(const zg_method *method, hipStream_t s, LutHolder 
     }
     h.dev = per_device[dev];
     return ZG_OK;
-}
-static void release_lut(LutHolder &h, hipStream_t s) {
-    if (h.owned) scratch_free(h.owned, s);
-    h.owned = nullptr;
 }
 
 static int check_method(const zg_method *method) {
@@ -172,8 +169,7 @@ static int launch_geom_k(const zg_image *src, const zg_image *dst, const GeomPar
     } else {
         hipLaunchKernelGGL((k_geom<PIX, KIND>), grid, dim3(256), 0, s, dimg(src), dimg(dst), g, m, border, tiles_x, fr);
     }
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 static int launch_geom(const zg_image *src, const zg_image *dst, const GeomParams &g, const zg_method *method, int border, hipStream_t s, const FrameBatch &fb = FrameBatch{}) {
@@ -181,12 +177,12 @@ static int launch_geom(const zg_image *src, const zg_image *dst, const GeomParam
     if ((rc = check_method(method))) return rc;
     ZG_REQUIRE(border >= ZG_BORDER_ZERO && border <= ZG_BORDER_WRAP, ZG_ERR_INVALID_ARGUMENT, "invalid border %d", border);
     if (dst->rows == 0 || dst->cols == 0) return ZG_OK;
-    LutHolder lut;
+    LutHolder lut(s);
     if ((rc = device_lanczos_lut(method, s, lut))) return rc;
     const MethodArg m{method->kind, method->b, method->c, lut.dev};
     GeomParams gp = g;
     gp.stage = 1;
-    rc = dispatch_pixel(src->pixel, [&](auto tag) -> int {
+    return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         switch (method->kind) {
         case ZG_INTERP_NEAREST: return launch_geom_k<PIX, ZG_INTERP_NEAREST>(src, dst, gp, m, border, fb, s);
@@ -197,8 +193,6 @@ static int launch_geom(const zg_image *src, const zg_image *dst, const GeomParam
         default: return launch_geom_k<PIX, ZG_INTERP_LANCZOS>(src, dst, gp, m, border, fb, s);
         }
     });
-    release_lut(lut, s);
-    return rc;
 }
 
 static int check_pair(const zg_image *src, const zg_image *dst, const char *op) {
@@ -424,12 +418,10 @@ static int launch_resize_bilinear_u8(const zg_image *src, const zg_image *dst, u
         if (R == 8) hipLaunchKernelGGL((k_resize_bilinear_u8_rows<8>), dim3((unsigned)tiles_r, n), dim3(256), 0, s, dimg(src), dimg(dst), rx, (float)src->rows / (float)dst->rows, tiles_x, fr, dword_rows);
         else if (R == 4) hipLaunchKernelGGL((k_resize_bilinear_u8_rows<4>), dim3((unsigned)tiles_r, n), dim3(256), 0, s, dimg(src), dimg(dst), rx, (float)src->rows / (float)dst->rows, tiles_x, fr, dword_rows);
         else hipLaunchKernelGGL((k_resize_bilinear_u8_rows<2>), dim3((unsigned)tiles_r, n), dim3(256), 0, s, dimg(src), dimg(dst), rx, (float)src->rows / (float)dst->rows, tiles_x, fr, dword_rows);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     }
     hipLaunchKernelGGL(k_resize_bilinear_u8, dim3((unsigned)tiles, n), dim3(256), 0, s, dimg(src), dimg(dst), rx, (float)src->rows / (float)dst->rows, tiles_x, fr, dword_rows);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 static bool resize_u8_plane_applies(const zg_image *src, const zg_image *dst, const zg_method *method) {
     return src->pixel == ZG_PIXEL_U8 && method->kind == ZG_INTERP_BILINEAR && src->rows > 0 && src->cols > 0 && dst->rows > 0 && dst->cols > 0;
@@ -594,7 +586,7 @@ static int rotate_into_impl(const zg_image *src, const zg_image *dst, float angl
 #define ZG_ROT(PS) case PS: hipLaunchKernelGGL(k_rotate_orthogonal<PS>, grid, dim3(256), 0, s, dimg(src), dimg(dst), oc, (int)off_r, (int)off_c); break;
             switch ((int)pixel_size(src->pixel)) { ZG_ROT(1) ZG_ROT(3) ZG_ROT(4) ZG_ROT(12) ZG_ROT(16) }
 #undef ZG_ROT
-            ZG_HIP(hipGetLastError());
+            if (const int e = launch_ok()) return e;
         }
         if (off_r != 0 || off_c != 0) {
             const uint32_t inner[4] = {off_c, off_r, off_c + rcols, off_r + rr};
@@ -634,8 +626,7 @@ static int copy_rect_impl(const zg_image *src, int rect_top, int rect_left, cons
 #define ZG_CR(PS) case PS: hipLaunchKernelGGL(k_copy_rect<PS>, grid, dim3(256), 0, s, dimg(src), dimg(out), rect_top, rect_left, border); break;
     switch ((int)pixel_size(src->pixel)) { ZG_CR(1) ZG_CR(3) ZG_CR(4) ZG_CR(12) ZG_CR(16) }
 #undef ZG_CR
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 static int extract_impl(const zg_image *src, const zg_image *dst, const float rect[4], float angle, float cos_a, float sin_a,
@@ -854,7 +845,7 @@ static int insert_impl(const zg_image *self, const zg_image *source, const float
         q.max_c = (int)std::min<double>(self->cols, (double)std::ceil(q.cx + bound_hw) + 1);
     }
     if (q.min_r >= q.max_r || q.min_c >= q.max_c) return ZG_OK;
-    LutHolder lut;
+    LutHolder lut(s);
     if ((rc = device_lanczos_lut(method, s, lut))) return rc;
     const MethodArg m{method->kind, method->b, method->c, lut.dev};
     const dim3 grid(ceil_div((unsigned)(q.max_c - q.min_c), 64), ceil_div((unsigned)(q.max_r - q.min_r), 4));
@@ -863,14 +854,16 @@ static int insert_impl(const zg_image *self, const zg_image *source, const float
     const bool mixed = self->pixel != source->pixel;
     const int bw = q.max_c - q.min_c, bh = q.max_r - q.min_r;
     zg_image target = *self;
+    ScratchBlock block(s); // after lut: released before it
     char *scratch = nullptr;
     if (mixed) {
         const size_t sps = pixel_size(source->pixel), samples_bytes = ((size_t)bw * bh * sps + 15) / 16 * 16;
-        if ((rc = scratch_alloc((void **)&scratch, samples_bytes + (size_t)bw * bh, s))) { release_lut(lut, s); return rc; }
+        if ((rc = block.alloc(samples_bytes + (size_t)bw * bh))) return rc;
+        scratch = block.p;
         q.mask = (uint8_t *)(scratch + samples_bytes);
         q.mask_w = bw;
         q.blend = 0;
-        if ((rc = fill_async(q.mask, 0, (size_t)bw * bh, s))) { scratch_free(scratch, s); release_lut(lut, s); return rc; }
+        if ((rc = fill_async(q.mask, 0, (size_t)bw * bh, s))) return rc;
         // a view of the scratch addressed with self's coordinates: pixel (min_r, min_c) is scratch[0], row pitch = box width
         target.pixel = source->pixel;
         target.stride = (size_t)bw;
@@ -884,27 +877,21 @@ static int insert_impl(const zg_image *self, const zg_image *source, const float
             ZG_INS(ZG_INTERP_CATMULL_ROM) ZG_INS(ZG_INTERP_MITCHELL) ZG_INS(ZG_INTERP_LANCZOS)
         }
 #undef ZG_INS
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
-    if (mixed) {
-        if (rc == ZG_OK)
-            rc = dispatch_pixel(source->pixel, [&](auto stag) -> int {
-                constexpr int SPIX = decltype(stag)::value;
-                return dispatch_pixel(self->pixel, [&](auto dtag) -> int {
-                    constexpr int DPIX = decltype(dtag)::value;
-                    if constexpr (SPIX != DPIX) {
-                        hipLaunchKernelGGL((k_insert_assign<SPIX, DPIX>), grid, dim3(256), 0, s, dimg(self), (const void *)scratch, (const uint8_t *)q.mask, q.min_r,
-                                           q.max_r, q.min_c, q.max_c, blend_mode);
-                        ZG_HIP(hipGetLastError());
-                    }
-                    return ZG_OK;
-                });
-            });
-        scratch_free(scratch, s);
-    }
-    release_lut(lut, s);
-    return rc;
+    if (rc || !mixed) return rc;
+    return dispatch_pixel(source->pixel, [&](auto stag) -> int {
+        constexpr int SPIX = decltype(stag)::value;
+        return dispatch_pixel(self->pixel, [&](auto dtag) -> int {
+            constexpr int DPIX = decltype(dtag)::value;
+            if constexpr (SPIX != DPIX) {
+                hipLaunchKernelGGL((k_insert_assign<SPIX, DPIX>), grid, dim3(256), 0, s, dimg(self), (const void *)scratch, (const uint8_t *)q.mask, q.min_r,
+                                   q.max_r, q.min_c, q.max_c, blend_mode);
+                if (const int e = launch_ok()) return e;
+            }
+            return ZG_OK;
+        });
+    });
 }
 
 } // namespace zg

@@ -21,6 +21,7 @@
 #include "zg_common.h"
 #include "zg_devmath.h"
 #include "zg_hostmath.h"
+#include "zg_scan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -61,28 +62,6 @@ struct ListArgs {
     int32_t x0, y0;        // x_val = 2 * col + x0, y_val = 2 * row + y0 (col, row relative to the area)
     uint32_t *list, *n;
 };
-
-// the calling thread's exclusive sum of v over the workgroup's 256 threads, and the sum of all in *total
-__device__ inline uint32_t block_exclusive_sum(uint32_t v, uint32_t *total) {
-    __shared__ uint32_t wave_sum[4];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off);
-        if ((int)lane >= off) incl += up;
-    }
-    __syncthreads(); // the previous call's reads of wave_sum are done
-    if (lane == 63u) wave_sum[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-    for (uint32_t k = 0; k < 4; ++k) {
-        base += k < wv ? wave_sum[k] : 0u;
-        all += wave_sum[k];
-    }
-    *total = all;
-    return base + incl - v;
-}
 
 constexpr uint32_t LIST_PER_THREAD = 16; // pixels a thread of k_edge_list looks at: a workgroup appends once for 4096 of them
 
@@ -336,20 +315,6 @@ __global__ __launch_bounds__(256) void k_lines(GreedyArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return ZG_OK;
-}
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Scratch {
-    char *p = nullptr;
-    hipStream_t s;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() { if (p) scratch_free(p, s); }
-};
-
 bool direct_forced() { // the replaced form stays reachable: read once per process
     static const bool forced = [] {
         const char *e = std::getenv("ZIGNAL_HIP_HOUGH_DIRECT");
@@ -414,10 +379,13 @@ int compute(zg_hough_t h, const zg_image *edges, uint32_t l, uint32_t t, uint32_
     if (al >= ar || at >= ab) return ZG_OK;
     const uint32_t w = ar - al, ht = ab - at, size = h->size;
     const uint64_t area = (uint64_t)w * ht;
-    Scratch sc(s);
+    // scratch: [the list's length][the list]
+    ScratchBlock sc(s);
+    uint32_t *n, *list;
+    sc.take(n, 1);
+    sc.take(list, area);
     int rc;
-    if ((rc = scratch_alloc((void **)&sc.p, 256 + (size_t)area * sizeof(uint32_t), s))) return rc;
-    uint32_t *n = (uint32_t *)sc.p, *list = (uint32_t *)(sc.p + 256);
+    if ((rc = sc.alloc())) return rc;
     if ((rc = fill_async(n, 0, sizeof(uint32_t), s))) return rc;
     const int32_t size_minus_one = (int32_t)size - 1;
     ListArgs la{(const uint8_t *)edges->data, edges->stride, al, at, w, ht, -size_minus_one, -size_minus_one, list, n};
@@ -457,26 +425,34 @@ int find_lines(zg_hough_t h, const uint32_t *accumulator, size_t acc_stride, uin
     if (size < 3) return fill_async(counts, 0, 2 * sizeof(uint32_t), s); // :154
     const uint32_t inner = size - 2, maxc = std::max(max_candidates, 1u);
     // scratch: [row counts][row offsets][candidates][sorted][kept angle][kept radius][kept]
-    const size_t rows_b = align256((size_t)inner * sizeof(uint32_t)), keys_b = align256((size_t)maxc * sizeof(uint64_t)),
-                 words_b = align256((size_t)maxc * sizeof(uint32_t));
-    Scratch sc(s);
-    int rc;
-    if ((rc = scratch_alloc((void **)&sc.p, 2 * rows_b + 2 * keys_b + 3 * words_b, s))) return rc;
     PeakArgs pa{};
+    GreedyArgs ga{};
+    ScratchBlock sc(s);
+    sc.take(pa.row_counts, inner);
+    sc.take(pa.row_offsets, inner);
+    sc.take(pa.cand, maxc);
+    sc.take(pa.sorted, maxc);
+    sc.take(ga.kept_angle, maxc);
+    sc.take(ga.kept_radius, maxc);
+    sc.take(ga.kept, maxc);
+    int rc;
+    if ((rc = sc.alloc())) return rc;
     pa.acc = accumulator;
     pa.acc_stride = acc_stride;
     pa.size = size;
     pa.threshold = threshold;
     pa.threshold_device = threshold_device;
     pa.max_candidates = max_candidates;
-    pa.row_counts = (uint32_t *)sc.p;
-    pa.row_offsets = (uint32_t *)(sc.p + rows_b);
-    pa.cand = (uint64_t *)(sc.p + 2 * rows_b);
-    pa.sorted = (uint64_t *)(sc.p + 2 * rows_b + keys_b);
     pa.counts = counts;
-    char *rest = sc.p + 2 * rows_b + 2 * keys_b;
-    GreedyArgs ga{pa.sorted, size, h->even_size, max_candidates, angle_thresh, radius_thresh, (float *)rest, (float *)(rest + words_b),
-                  (uint32_t *)(rest + 2 * words_b), lines, capacity, counts};
+    ga.sorted = pa.sorted;
+    ga.size = size;
+    ga.even_size = h->even_size;
+    ga.max_candidates = max_candidates;
+    ga.angle_thresh = angle_thresh;
+    ga.radius_thresh = radius_thresh;
+    ga.lines = lines;
+    ga.capacity = capacity;
+    ga.counts = counts;
     hipLaunchKernelGGL(k_peak_rows<false>, dim3(inner), dim3(256), 0, s, pa);
     if ((rc = launch_ok("k_peak_rows<count>"))) return rc;
     hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(256), 0, s, pa);
@@ -563,8 +539,8 @@ int zg_hough_compute_host(zg_hough_t h, const zg_image *edges, uint32_t l, uint3
     const size_t row_b = (size_t)size * sizeof(uint32_t);
     HostStage e;
     if ((rc = e.upload(edges, true, false))) return rc;
-    Scratch sc(nullptr);
-    if ((rc = scratch_alloc((void **)&sc.p, row_b * size, nullptr))) return rc;
+    ScratchBlock sc;
+    if ((rc = sc.alloc(row_b * size))) return rc;
     if ((rc = upload_pageable_rows(sc.p, accumulator, acc_stride * sizeof(uint32_t), row_b, size, nullptr))) return rc;
     if ((rc = compute(h, &e.dev, l, t, r, b, (uint32_t *)sc.p, size, nullptr))) return rc;
     return download_pageable_rows(accumulator, acc_stride * sizeof(uint32_t), sc.p, row_b, size, nullptr);
@@ -575,18 +551,20 @@ int zg_hough_find_lines_host(zg_hough_t h, const uint32_t *accumulator, size_t a
     int rc;
     if ((rc = check_find(h, accumulator, acc_stride, max_candidates, lines, capacity, counts))) return rc;
     const uint32_t size = h->size, cap = std::min(capacity, max_candidates);
-    const size_t row_b = (size_t)size * sizeof(uint32_t), acc_b = align256(row_b * size), lines_b = align256((size_t)cap * sizeof(zg_hough_line));
-    Scratch sc(nullptr);
-    if ((rc = scratch_alloc((void **)&sc.p, acc_b + lines_b + 256, nullptr))) return rc;
-    if ((rc = upload_pageable_rows(sc.p, accumulator, acc_stride * sizeof(uint32_t), row_b, size, nullptr))) return rc;
-    zg_hough_line *dlines = (zg_hough_line *)(sc.p + acc_b);
-    uint32_t *dcounts = (uint32_t *)(sc.p + acc_b + lines_b);
-    if ((rc = find_lines(h, (const uint32_t *)sc.p, size, threshold, nullptr, angle_nms_thresh, radius_nms_thresh, max_candidates, cap ? dlines : nullptr, cap,
-                         dcounts, nullptr)))
+    const size_t row_b = (size_t)size * sizeof(uint32_t);
+    // scratch: [accumulator][lines][counts]
+    ScratchBlock sc;
+    uint32_t *dacc, *dcounts;
+    zg_hough_line *dlines;
+    sc.take(dacc, (size_t)size * size);
+    sc.take(dlines, cap);
+    sc.take(dcounts, 2);
+    if ((rc = sc.alloc())) return rc;
+    if ((rc = upload_pageable_rows(dacc, accumulator, acc_stride * sizeof(uint32_t), row_b, size, nullptr))) return rc;
+    if ((rc = find_lines(h, dacc, size, threshold, nullptr, angle_nms_thresh, radius_nms_thresh, max_candidates, cap ? dlines : nullptr, cap, dcounts,
+                         nullptr)))
         return rc;
-    if ((rc = download_pageable(counts, dcounts, 2 * sizeof(uint32_t), nullptr))) return rc;
-    const size_t n = std::min(counts[1], cap);
-    return n ? download_pageable(lines, dlines, n * sizeof(zg_hough_line), nullptr) : ZG_OK;
+    return download_counted(counts, dcounts, 2, lines, dlines, cap);
 }
 
 } // extern "C"

@@ -43,8 +43,7 @@ int fill_outside_impl(const zg_image *img, const void *pixel_value, int l, int t
     const int ps = (int)pixel_size(img->pixel);
     if (pixel_value) std::memcpy(v.b, pixel_value, (size_t)ps);
     hipLaunchKernelGGL(k_fill_outside, row_grid(ceil_div(img->cols, 256), img->rows), dim3(256), 0, s, dimg(img), ps, v, l, t, r, b);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // setBorder: rect clipped to the image; an empty intersection fills everything (image.zig:200-204).
@@ -98,8 +97,7 @@ static int flip_impl(const zg_image *img, bool lr, hipStream_t s) {
         ZG_FLIP(1) ZG_FLIP(3) ZG_FLIP(4) ZG_FLIP(12) ZG_FLIP(16)
     }
 #undef ZG_FLIP
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // Image(T).invert (image.zig:494-513): u8 scalars 255 - v; colour structs through their .invert() (color.zig:328-331,
@@ -128,8 +126,7 @@ static int invert_impl(const zg_image *img, hipStream_t s) {
     return dispatch_pixel(img->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         hipLaunchKernelGGL((k_invert<PIX>), row_grid(ceil_div(img->cols, 256), img->rows), dim3(256), 0, s, dimg(img));
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
 }
 
@@ -149,8 +146,7 @@ int fill_async(void *p, uint8_t value, size_t bytes, hipStream_t s) {
     const uint32_t word = 0x01010101u * value;
     const size_t blocks = std::min<size_t>(1024, std::max<size_t>(1, (std::max(words, bytes - words * 4) + 255) / 256));
     hipLaunchKernelGGL(k_fill, dim3((unsigned)blocks), dim3(256), 0, s, (uint8_t *)p, word, words, bytes);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 } // namespace zg

@@ -527,8 +527,7 @@ int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_
     if (!isef_2d_applies(rows, cols) || ((uintptr_t)gray & 15) || ((uintptr_t)sm & 15) || ((uintptr_t)tmp & 15)) return -1;
     if (gray_is_bytes) isef_2d_launch<true>(gray, sm, tmp, check, rows, cols, smooth, s);
     else isef_2d_launch<false>(gray, sm, tmp, check, rows, cols, smooth, s);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 } // namespace zg

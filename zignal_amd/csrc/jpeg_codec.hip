@@ -866,12 +866,13 @@ int decode_impl(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits, c
     const bool direct = dst->pixel == native && dst_space == natural_space(native);
     const size_t native_bytes = direct ? 0 : (size_t)d.header.width * d.header.height * pixel_size(native);
     // scratch: coefficients | sample planes (same sizes) | native image when a conversion follows
-    int32_t *dev = nullptr;
-    if ((rc = scratch_alloc((void **)&dev, coef_words * 2 * sizeof(int32_t) + native_bytes + 256, s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc(coef_words * 2 * sizeof(int32_t) + native_bytes + 256))) return rc;
+    int32_t *dev = (int32_t *)block.p;
     rc = upload_pageable(dev, d.coef[0].data(), luma_coefs * sizeof(int32_t), s); // the host buffers die with this call
     for (int c = 0; c < 2 && nc == 3 && rc == ZG_OK; ++c)
         rc = upload_pageable(dev + luma_coefs + (size_t)c * chroma_coefs, chroma[c], chroma_coefs * sizeof(int32_t), s);
-    if (rc) { scratch_free(dev, s); return rc; }
+    if (rc) return rc;
 
     int32_t *planes = dev + coef_words;
     for (int c = 0; c < nc; ++c) {
@@ -887,10 +888,8 @@ int decode_impl(const uint8_t *jpeg, size_t len, const zg_jpeg_limits *limits, c
     const dim3 grid(ceil_div(d.header.width, 256), d.header.height);
     if (native == ZG_PIXEL_U8) hipLaunchKernelGGL((k_jpeg_render<ZG_PIXEL_U8>), grid, dim3(256), 0, s, a, dimg(target));
     else hipLaunchKernelGGL((k_jpeg_render<ZG_PIXEL_RGB_U8>), grid, dim3(256), 0, s, a, dimg(target));
-    rc = hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
-    if (rc == ZG_OK && !direct) rc = zg_convert(&native_img, natural_space(native), dst, dst_space, nullptr, (zg_stream)s); // Image.convert (:2831-2850)
-    scratch_free(dev, s);
-    return rc;
+    if ((rc = launch_ok("k_jpeg_idct / k_jpeg_render")) || direct) return rc;
+    return zg_convert(&native_img, natural_space(native), dst, dst_space, nullptr, (zg_stream)s); // Image.convert (:2831-2850)
 }
 
 // ==== encoder (jpeg.zig:293-1043) ================================================================================================
@@ -1262,8 +1261,9 @@ int encode_impl(const zg_image *src, int src_space, const zg_jpeg_encode_options
     const unsigned lbx = mcus_x * hm, lby = mcus_y * vm;
     const size_t luma_blocks = (size_t)lbx * lby, chroma_blocks = gray ? 0 : (size_t)mcus_x * mcus_y, total_blocks = luma_blocks + 2 * chroma_blocks;
     const size_t rgb_bytes = direct ? 0 : ((size_t)src->rows * src->cols * 3 + 255) / 256 * 256;
-    char *dev = nullptr;
-    if ((rc = scratch_alloc((void **)&dev, rgb_bytes + total_blocks * 64 * sizeof(int16_t), s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc(rgb_bytes + total_blocks * 64 * sizeof(int16_t)))) return rc;
+    char *dev = block.p;
     zg_image rgb{dev, src->cols, src->rows, src->cols, ZG_PIXEL_RGB_U8};
     if (!direct) rc = zg_convert(src, src_space, &rgb, ZG_CS_RGB, nullptr, (zg_stream)s); // image.convert(Rgb) (:323-327)
     const zg_image *img = direct ? src : &rgb;
@@ -1279,14 +1279,14 @@ int encode_impl(const zg_image *src, int src_space, const zg_jpeg_encode_options
             if (gray) hipLaunchKernelGGL((k_jpeg_forward<true>), dim3(ceil_div(a.nblocks, 32)), dim3(256), 0, s, a, rl, dstc);
             else hipLaunchKernelGGL((k_jpeg_forward<false>), dim3(ceil_div(a.nblocks, 32)), dim3(256), 0, s, a, c == 0 ? rl : rcq, dstc);
         }
-        if (hipGetLastError() != hipSuccess) rc = ZG_ERR_HIP;
+        rc = launch_ok("k_jpeg_forward");
     }
     std::vector<int16_t> host;
     if (rc == ZG_OK) {
         host.resize(total_blocks * 64);
         rc = download_pageable(host.data(), coef, host.size() * sizeof(int16_t), s);
     }
-    scratch_free(dev, s);
+    block.reset(); // before the entropy coding on the host
     if (rc) return rc;
 
     std::vector<uint8_t> file;

@@ -18,6 +18,7 @@
 //            k_rows<RADIUS>   both passes, placing at the row's offset
 // No atomic decides an order: the LDS counters are sums, every position is computed.
 #include "zg_common.h"
+#include "zg_scan.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -142,12 +143,7 @@ __device__ inline uint32_t grid_exclusive_sum(const uint32_t *values, uint32_t n
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, first = blockIdx.x * 256u;
     uint32_t before = 0;
     for (uint32_t i = tid; i < first; i += 256u) before += values[i];
-    uint32_t v = first + tid < n ? values[first + tid] : 0u, incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off);
-        if ((int)lane >= off) incl += up;
-    }
+    const uint32_t v = first + tid < n ? values[first + tid] : 0u, incl = wave_inclusive_sum(v);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
     if (lane == 63u) wave_sum[wv] = incl;
@@ -211,13 +207,7 @@ template <int MODE> __global__ __launch_bounds__(256) void k_rows(RowArgs a) {
         // first[d] = entries nearer than d: lane l owns bins 4 l .. 4 l + 3, bin 256 follows them all
         const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
         const uint32_t mine = h0 + h1 + h2 + h3;
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off);
-            if ((int)lane >= off) incl += up;
-        }
-        const uint32_t ex = incl - mine;
+        const uint32_t incl = wave_inclusive_sum(mine), ex = incl - mine;
         first[4 * lane] = ex;
         first[4 * lane + 1] = ex + h0;
         first[4 * lane + 2] = ex + h0 + h1;
@@ -273,20 +263,6 @@ __global__ __launch_bounds__(256) void k_row_offsets(OffsetArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return ZG_OK;
-}
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Scratch {
-    char *p = nullptr;
-    hipStream_t s;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() { if (p) scratch_free(p, s); }
-};
-
 int check_set(const zg_descriptor_set *s, const char *name) {
     ZG_REQUIRE(s != nullptr, ZG_ERR_INVALID_ARGUMENT, "match: null %s set", name);
     ZG_REQUIRE(s->data != nullptr || s->capacity == 0, ZG_ERR_INVALID_ARGUMENT, "match: %s has capacity %u and null data", name, s->capacity);
@@ -319,19 +295,20 @@ int match(const zg_descriptor_set *query, const zg_descriptor_set *train, const 
     a.capacity = capacity;
     a.count = count;
     // scratch: [forward partials][reverse partials][cand][keep]
-    const size_t fwd_b = align256((size_t)a.split_f * cq * sizeof(Partial)), rev_b = align256((size_t)a.split_r * ct * sizeof(Partial));
-    const size_t cand_b = align256((size_t)cq * sizeof(uint2)), keep_b = align256((size_t)cq * sizeof(uint32_t));
-    Scratch sc(s);
+    ScratchBlock sc(s);
+    Partial *fwd, *rev;
+    sc.take(fwd, (size_t)a.split_f * cq);
+    sc.take(rev, (size_t)a.split_r * ct);
+    sc.take(a.cand, cq);
+    sc.take(a.keep, cq);
     int rc;
-    if ((rc = scratch_alloc((void **)&sc.p, fwd_b + rev_b + cand_b + keep_b, s))) return rc;
-    a.fwd = (const Partial *)sc.p;
-    a.rev = p->cross_check ? (const Partial *)(sc.p + fwd_b) : nullptr;
-    a.cand = (uint2 *)(sc.p + fwd_b + rev_b);
-    a.keep = (uint32_t *)(sc.p + fwd_b + rev_b + cand_b);
-    hipLaunchKernelGGL(k_nearest, dim3(ceil_div(cq, 64), a.split_f), dim3(64), 0, s, a.query, a.train, (Partial *)sc.p);
+    if ((rc = sc.alloc())) return rc;
+    a.fwd = fwd;
+    a.rev = p->cross_check ? rev : nullptr;
+    hipLaunchKernelGGL(k_nearest, dim3(ceil_div(cq, 64), a.split_f), dim3(64), 0, s, a.query, a.train, fwd);
     if ((rc = launch_ok("k_nearest"))) return rc;
     if (p->cross_check) {
-        hipLaunchKernelGGL(k_nearest, dim3(ceil_div(ct, 64), a.split_r), dim3(64), 0, s, a.train, a.query, (Partial *)(sc.p + fwd_b));
+        hipLaunchKernelGGL(k_nearest, dim3(ceil_div(ct, 64), a.split_r), dim3(64), 0, s, a.train, a.query, rev);
         if ((rc = launch_ok("k_nearest (cross-check)"))) return rc;
     }
     hipLaunchKernelGGL(k_match_decide, dim3(ceil_div(cq, 64)), dim3(64), 0, s, a);
@@ -372,8 +349,8 @@ int radius(const zg_descriptor_set *query, const zg_descriptor_set *train, float
     a.out = matches;
     a.capacity = capacity;
     a.row_counts = row_counts;
-    Scratch sc(s);
-    if ((rc = scratch_alloc((void **)&sc.p, align256((size_t)cq * sizeof(uint32_t)), s))) return rc;
+    ScratchBlock sc(s);
+    if ((rc = sc.alloc(align256((size_t)cq * sizeof(uint32_t))))) return rc;
     a.offsets = (const uint32_t *)sc.p;
     hipLaunchKernelGGL(k_rows<ROWS_COUNT>, dim3(row_blocks(cq)), dim3(256), 0, s, a);
     if ((rc = launch_ok("k_rows<count>"))) return rc;
@@ -400,19 +377,19 @@ struct Staged {
     uint32_t n = 0;
 };
 uint32_t host_size(const zg_descriptor_set *s) { return s->count ? std::min(*s->count, s->capacity) : s->capacity; }
-// Both sets and `extra` more bytes in one block: [query][train][extra].
-int stage(const zg_descriptor_set *query, const zg_descriptor_set *train, size_t extra, Scratch *sc, Staged *q, Staged *t, char **rest) {
+// Both sets at the head of a block whose other parts the caller has still to take: [query][train][the caller's parts]. stage_upload
+// follows the block's alloc().
+void stage(const zg_descriptor_set *query, const zg_descriptor_set *train, ScratchBlock *sc, Staged *q, Staged *t) {
     q->n = host_size(query);
     t->n = host_size(train);
-    const size_t qb = align256((size_t)q->n * 32), tb = align256((size_t)t->n * 32);
-    int rc;
-    if ((rc = scratch_alloc((void **)&sc->p, qb + tb + extra + 256, nullptr))) return rc;
-    if (q->n && (rc = upload_pageable(sc->p, query->data, (size_t)q->n * 32, nullptr))) return rc;
-    if (t->n && (rc = upload_pageable(sc->p + qb, train->data, (size_t)t->n * 32, nullptr))) return rc;
-    q->set = zg_descriptor_set{(const zg_binary_descriptor *)sc->p, q->n, nullptr};
-    t->set = zg_descriptor_set{(const zg_binary_descriptor *)(sc->p + qb), t->n, nullptr};
-    *rest = sc->p + qb + tb;
-    return ZG_OK;
+    q->set = zg_descriptor_set{nullptr, q->n, nullptr};
+    t->set = zg_descriptor_set{nullptr, t->n, nullptr};
+    sc->take(q->set.data, q->n);
+    sc->take(t->set.data, t->n);
+}
+int stage_upload(const zg_descriptor_set *query, const zg_descriptor_set *train, const Staged &q, const Staged &t) {
+    if (const int rc = upload_pageable((void *)q.set.data, query->data, (size_t)q.n * 32, nullptr)) return rc;
+    return upload_pageable((void *)t.set.data, train->data, (size_t)t.n * 32, nullptr);
 }
 
 } // namespace
@@ -463,16 +440,17 @@ int zg_match_descriptors_host(const zg_descriptor_set *query, const zg_descripto
     if ((rc = check_set(query, "query")) || (rc = check_set(train, "train")) || (rc = check_params(params))) return rc;
     ZG_REQUIRE(count != nullptr, ZG_ERR_INVALID_ARGUMENT, "match: null count");
     ZG_REQUIRE(matches != nullptr || capacity == 0, ZG_ERR_INVALID_ARGUMENT, "match: null matches with capacity %u", capacity);
-    Scratch sc(nullptr);
+    ScratchBlock sc;
     Staged q, t;
-    char *rest;
-    const uint32_t cap = std::min(capacity, host_size(query)); // a match per query at the most
-    if ((rc = stage(query, train, align256((size_t)cap * sizeof(zg_match)), &sc, &q, &t, &rest))) return rc;
-    uint32_t *dcount = (uint32_t *)(rest + align256((size_t)cap * sizeof(zg_match)));
-    if ((rc = match(&q.set, &t.set, params, cap ? (zg_match *)rest : nullptr, cap, dcount, nullptr))) return rc;
-    if ((rc = download_pageable(count, dcount, sizeof(uint32_t), nullptr))) return rc;
-    const size_t n = std::min(*count, cap);
-    return n ? download_pageable(matches, rest, n * sizeof(zg_match), nullptr) : ZG_OK;
+    stage(query, train, &sc, &q, &t);
+    const uint32_t cap = std::min(capacity, q.n); // a match per query at the most
+    zg_match *dout;
+    uint32_t *dcount;
+    sc.take(dout, cap);
+    sc.take(dcount, 1);
+    if ((rc = sc.alloc()) || (rc = stage_upload(query, train, q, t))) return rc;
+    if ((rc = match(&q.set, &t.set, params, cap ? dout : nullptr, cap, dcount, nullptr))) return rc;
+    return download_counted(count, dcount, 1, matches, dout, cap);
 }
 
 int zg_match_knn_host(const zg_descriptor_set *query, const zg_descriptor_set *train, const zg_matcher_params *params, uint32_t k, zg_match *matches,
@@ -480,21 +458,24 @@ int zg_match_knn_host(const zg_descriptor_set *query, const zg_descriptor_set *t
     int rc;
     if ((rc = check_set(query, "query")) || (rc = check_set(train, "train")) || (rc = check_params(params)) || (rc = check_knn(query, k))) return rc;
     ZG_REQUIRE(row_counts != nullptr || query->capacity == 0, ZG_ERR_INVALID_ARGUMENT, "match knn: null row_counts");
-    Scratch sc(nullptr);
+    ScratchBlock sc;
     Staged q, t;
-    char *rest;
-    const uint32_t nq = host_size(query);
-    const size_t out_b = align256((size_t)nq * k * sizeof(zg_match));
-    if ((rc = stage(query, train, out_b + align256((size_t)nq * sizeof(uint32_t)), &sc, &q, &t, &rest))) return rc;
-    uint32_t *drows = (uint32_t *)(rest + out_b);
-    if ((rc = knn(&q.set, &t.set, params, k, (zg_match *)rest, drows, nullptr))) return rc;
+    stage(query, train, &sc, &q, &t);
+    const uint32_t nq = q.n;
+    zg_match *dout;
+    uint32_t *drows, *spare;
+    sc.take(dout, (size_t)nq * k);
+    sc.take(drows, nq);
+    sc.take(spare, 1); // the radius form's layout, [query][train][matches][row counts][count]: the two share a cached block
+    if ((rc = sc.alloc()) || (rc = stage_upload(query, train, q, t))) return rc;
+    if ((rc = knn(&q.set, &t.set, params, k, dout, drows, nullptr))) return rc;
     for (uint32_t i = nq; i < query->capacity; ++i) row_counts[i] = 0;
     if (nq == 0) return ZG_OK;
     if ((rc = download_pageable(row_counts, drows, (size_t)nq * sizeof(uint32_t), nullptr))) return rc;
     if (!matches || k == 0) return ZG_OK;
     // rows are k apart and only their first row_counts[q] entries are defined: copy those
     std::unique_ptr<zg_match[]> all(new zg_match[(size_t)nq * k]);
-    if ((rc = download_pageable(all.get(), rest, (size_t)nq * k * sizeof(zg_match), nullptr))) return rc;
+    if ((rc = download_pageable(all.get(), dout, (size_t)nq * k * sizeof(zg_match), nullptr))) return rc;
     for (uint32_t i = 0; i < nq; ++i) std::copy_n(all.get() + (size_t)i * k, row_counts[i], matches + (size_t)i * k);
     return ZG_OK;
 }
@@ -505,22 +486,23 @@ int zg_match_radius_host(const zg_descriptor_set *query, const zg_descriptor_set
     if ((rc = check_set(query, "query")) || (rc = check_set(train, "train")) || (rc = check_radius(query, train))) return rc;
     ZG_REQUIRE(count != nullptr, ZG_ERR_INVALID_ARGUMENT, "match radius: null count");
     ZG_REQUIRE(matches != nullptr || capacity == 0, ZG_ERR_INVALID_ARGUMENT, "match radius: null matches with capacity %u", capacity);
-    Scratch sc(nullptr);
+    ScratchBlock sc;
     Staged q, t;
-    char *rest;
-    const uint32_t nq = host_size(query);
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)nq * host_size(train));
-    const size_t out_b = align256((size_t)cap * sizeof(zg_match)), rows_b = align256((size_t)nq * sizeof(uint32_t));
-    if ((rc = stage(query, train, out_b + rows_b, &sc, &q, &t, &rest))) return rc;
-    uint32_t *drows = (uint32_t *)(rest + out_b), *dcount = (uint32_t *)(rest + out_b + rows_b);
-    if ((rc = radius(&q.set, &t.set, max_dist, cap ? (zg_match *)rest : nullptr, cap, drows, dcount, nullptr))) return rc;
-    if ((rc = download_pageable(count, dcount, sizeof(uint32_t), nullptr))) return rc;
+    stage(query, train, &sc, &q, &t);
+    const uint32_t nq = q.n;
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)nq * t.n);
+    zg_match *dout;
+    uint32_t *drows, *dcount;
+    sc.take(dout, cap);
+    sc.take(drows, nq);
+    sc.take(dcount, 1);
+    if ((rc = sc.alloc()) || (rc = stage_upload(query, train, q, t))) return rc;
+    if ((rc = radius(&q.set, &t.set, max_dist, cap ? dout : nullptr, cap, drows, dcount, nullptr))) return rc;
     if (row_counts) {
         for (uint32_t i = nq; i < query->capacity; ++i) row_counts[i] = 0;
         if (nq && (rc = download_pageable(row_counts, drows, (size_t)nq * sizeof(uint32_t), nullptr))) return rc;
     }
-    const size_t n = std::min(*count, cap);
-    return n ? download_pageable(matches, rest, n * sizeof(zg_match), nullptr) : ZG_OK;
+    return download_counted(count, dcount, 1, matches, dout, cap);
 }
 
 int zg_match_stats(const zg_match *matches, size_t n, zg_match_statistics *out) {

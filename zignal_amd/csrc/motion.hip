@@ -157,8 +157,7 @@ static int motion_linear_frames_impl(const zg_image *src, const zg_image *dst, u
             const dim3 grid(ceil_div(src->cols, 64), ceil_div(src->rows, 4), std::min(n - f0, 65535u));
             hipLaunchKernelGGL((k_motion_linear<PIX>), grid, dim3(256), 0, s, dimg(&a), dimg(&b), cos_a, sin_a, (float)distance / 2.0f, distance + 2, fr);
         }
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
 }
 
@@ -189,8 +188,7 @@ static int motion_radial_frames_impl(const zg_image *src, const zg_image *dst, u
             if (spin) hipLaunchKernelGGL((k_motion_radial<PIX, true>), grid, dim3(256), 0, s, dimg(&a), dimg(&b), cx, cy, clamped, num_samples, fr);
             else hipLaunchKernelGGL((k_motion_radial<PIX, false>), grid, dim3(256), 0, s, dimg(&a), dimg(&b), cx, cy, clamped, num_samples, fr);
         }
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
+        return launch_ok();
     });
 }
 

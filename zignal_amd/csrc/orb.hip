@@ -21,6 +21,7 @@
 #include "zg_internal.h"
 #include "zg_devmath.h"
 #include "zg_hostmath.h"
+#include "zg_scan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -174,13 +175,7 @@ __device__ inline void select_state(const OrbArgs &a, int j, int upto, uint64_t 
             } else {
                 const uint32_t *h = a.hist + ((size_t)j * 8 + q) * 256 + 4 * lane;
                 const uint32_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3];
-                const uint32_t sum = v0 + v1 + v2 + v3;
-                uint32_t incl = sum;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t t = __shfl_up(incl, off);
-                    if (lane >= off) incl += t;
-                }
+                const uint32_t sum = v0 + v1 + v2 + v3, incl = wave_inclusive_sum(sum);
                 const uint64_t reach = __ballot(incl >= k);
                 const int first = reach ? __ffsll((long long)reach) - 1 : 63; // reach != 0: the entries under the prefix are at least k
                 uint32_t kk = k - __shfl(incl - sum, first);
@@ -304,8 +299,7 @@ __global__ __launch_bounds__(64) void k_orb_orient(OrbArgs a) {
 
 // ---- the levels' lists, one after the other ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_orb_compact(OrbArgs a) {
-    __shared__ uint32_t wave_n[4];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = (int)threadIdx.x;
     uint32_t base = 0;
     for (int j = 0; j < a.n; ++j) {
         const OrbJob &J = a.job[j];
@@ -316,18 +310,10 @@ __global__ __launch_bounds__(256) void k_orb_compact(OrbArgs a) {
             kp.octave = -1;
             if (i < m) kp = a.tmp[J.sel_off + i];
             const bool keep = kp.octave >= 0;
-            const uint64_t ballot = __ballot(keep);
-            if (lane == 0) wave_n[wv] = (uint32_t)__popcll(ballot);
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-            for (int k = 0; k < 4; ++k) {
-                before += k < wv ? wave_n[k] : 0u;
-                total += wave_n[k];
-            }
-            before += (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+            uint32_t total;
+            const uint32_t before = block_exclusive_count(keep, &total);
             if (keep && base + before < a.capacity) a.out[base + before] = kp;
             base += total;
-            __syncthreads();
         }
     }
     if (tid == 0) *a.count = base;
@@ -369,13 +355,6 @@ __global__ __launch_bounds__(256) void k_orb_describe(OrbPyramid P, const zg_key
         }
     }
 }
-
-int launch_ok(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return ZG_OK;
-}
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 int check_params(const zg_orb_params *p) {
     ZG_REQUIRE(p != nullptr, ZG_ERR_INVALID_ARGUMENT, "orb: null params");
@@ -462,13 +441,6 @@ int make_plan(const zg_image *src, const zg_orb_params *p, bool device_pointer, 
     return ZG_OK;
 }
 
-struct Scratch {
-    char *p = nullptr;
-    hipStream_t s;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    ~Scratch() { if (p) scratch_free(p, s); }
-};
-
 // The pyramid's levels first .. n_levels - 1 (level 0 is the source) at base, packed; fills P and builds them on s.
 size_t pyramid_bytes(const Plan &plan, uint32_t first) {
     size_t b = 0;
@@ -537,36 +509,28 @@ int detect_and_compute(const zg_image *src, const zg_orb_params *p, const Plan &
     }
     const uint32_t first = (uint32_t)a.job[0].octave;
     // scratch: [pyramid levels][per job: pos, key][counts][hist, sel_n (zeroed)][sel][tmp][weights]
-    const size_t pyr_b = pyramid_bytes(plan, first);
-    size_t bytes = pyr_b;
-    std::vector<size_t> list_off(a.n);
+    const size_t zero_words = (size_t)a.n * 8 * 256 + a.n;
+    ScratchBlock sc(s);
+    char *pyramid;
+    float *weights;
+    sc.take(pyramid, pyramid_bytes(plan, first));
     for (int j = 0; j < a.n; ++j) {
-        list_off[j] = bytes;
-        bytes += 2 * align256((size_t)a.job[j].cand * sizeof(uint32_t));
+        sc.take(a.job[j].pos, a.job[j].cand);
+        sc.take(a.job[j].key, a.job[j].cand);
     }
-    const size_t counts_off = bytes;
-    bytes += align256((size_t)a.n * sizeof(uint32_t));
-    const size_t zero_off = bytes, zero_b = align256(((size_t)a.n * 8 * 256 + a.n) * sizeof(uint32_t));
-    bytes += zero_b;
-    const size_t sel_off = bytes;
-    bytes += align256((size_t)sel_total * sizeof(uint64_t));
-    const size_t tmp_off = bytes;
-    bytes += align256((size_t)sel_total * sizeof(zg_keypoint));
-    const size_t w_off = bytes;
-    bytes += align256(PATCH * PATCH * sizeof(float));
-    Scratch sc(s);
-    if ((rc = scratch_alloc((void **)&sc.p, bytes, s))) return rc;
+    sc.take(a.counts, a.n);
+    sc.take(a.hist, zero_words);
+    sc.take(a.sel, sel_total);
+    sc.take(a.tmp, sel_total);
+    sc.take(weights, PATCH * PATCH);
+    if ((rc = sc.alloc())) return rc;
     if (p->orientation_weights) {
-        if ((rc = upload_pageable(sc.p + w_off, p->orientation_weights, PATCH * PATCH * sizeof(float), s))) return rc;
-        a.weights = (const float *)(sc.p + w_off);
+        if ((rc = upload_pageable(weights, p->orientation_weights, PATCH * PATCH * sizeof(float), s))) return rc;
+        a.weights = weights;
     }
     OrbPyramid P{};
-    if ((rc = build_pyramid(src, plan, first, sc.p, &P, s))) return rc;
-    a.counts = (uint32_t *)(sc.p + counts_off);
-    a.hist = (uint32_t *)(sc.p + zero_off);
+    if ((rc = build_pyramid(src, plan, first, pyramid, &P, s))) return rc;
     a.sel_n = a.hist + (size_t)a.n * 8 * 256;
-    a.sel = (uint64_t *)(sc.p + sel_off);
-    a.tmp = (zg_keypoint *)(sc.p + tmp_off);
     a.out = keypoints;
     a.capacity = capacity;
     a.count = count;
@@ -577,8 +541,6 @@ int detect_and_compute(const zg_image *src, const zg_orb_params *p, const Plan &
         OrbJob &J = a.job[j];
         J.img = P.img[J.octave];
         J.stride = P.stride[J.octave];
-        J.pos = (uint32_t *)(sc.p + list_off[j]);
-        J.key = (uint32_t *)(sc.p + list_off[j] + align256((size_t)J.cand * sizeof(uint32_t)));
         images[j] = zg_image{(void *)J.img, (size_t)J.stride, (uint32_t)J.rows, (uint32_t)J.cols, ZG_PIXEL_U8};
         thresholds[j] = plan.threshold[J.octave];
         caps[j] = J.cand;
@@ -586,7 +548,7 @@ int detect_and_compute(const zg_image *src, const zg_orb_params *p, const Plan &
         key[j] = J.key;
         cnt[j] = a.counts + j;
     }
-    if ((rc = fill_async(sc.p + zero_off, 0, zero_b, s))) return rc;
+    if ((rc = fill_async(a.hist, 0, align256(zero_words * sizeof(uint32_t)), s))) return rc;
     if ((rc = fast_detect_compact(images.data(), (uint32_t)a.n, thresholds.data(), pos.data(), key.data(), caps.data(), cnt.data(), s))) return rc;
     const dim3 sweep(std::max(1u, std::min(ceil_div(max_cand, 256 * 8), 256u)), (unsigned)a.n);
     if (a.harris) {
@@ -612,10 +574,10 @@ int detect_and_compute(const zg_image *src, const zg_orb_params *p, const Plan &
 
 int compute(const zg_image *src, const Plan &plan, const zg_keypoint *keypoints, uint32_t n, zg_binary_descriptor *descriptors, hipStream_t s) {
     if (n == 0) return ZG_OK;
-    Scratch sc(s);
+    ScratchBlock sc(s);
     int rc;
     const size_t bytes = pyramid_bytes(plan, 1);
-    if (bytes && (rc = scratch_alloc((void **)&sc.p, bytes, s))) return rc;
+    if (bytes && (rc = sc.alloc(bytes))) return rc;
     OrbPyramid P{};
     if ((rc = build_pyramid(src, plan, 1, sc.p, &P, s))) return rc;
     return describe(P, keypoints, nullptr, n, descriptors, s);
@@ -676,18 +638,20 @@ int zg_orb_detect_and_compute_host(const zg_image *src, const zg_orb_params *par
     ZG_REQUIRE(keypoints != nullptr || capacity == 0, ZG_ERR_INVALID_ARGUMENT, "orb: null keypoints with capacity %u", capacity);
     HostStage in;
     if ((rc = in.upload(src, true, false))) return rc;
-    const size_t kp_b = align256((size_t)capacity * sizeof(zg_keypoint)), de_b = align256((size_t)capacity * sizeof(zg_binary_descriptor));
-    Scratch sc(nullptr);
-    if ((rc = scratch_alloc((void **)&sc.p, kp_b + de_b + 256, nullptr))) return rc;
-    zg_keypoint *dkp = capacity ? (zg_keypoint *)sc.p : nullptr;
-    zg_binary_descriptor *dde = capacity && descriptors ? (zg_binary_descriptor *)(sc.p + kp_b) : nullptr;
-    uint32_t *dcount = (uint32_t *)(sc.p + kp_b + de_b);
+    // scratch: [keypoints][descriptors][count]
+    ScratchBlock sc;
+    zg_keypoint *dkp;
+    zg_binary_descriptor *dde;
+    uint32_t *dcount;
+    sc.take(dkp, capacity);
+    sc.take(dde, capacity);
+    sc.take(dcount, 1);
+    if ((rc = sc.alloc())) return rc;
+    if (!capacity) dkp = nullptr;
+    if (!capacity || !descriptors) dde = nullptr;
     if ((rc = detect_and_compute(&in.dev, params, plan, dkp, dde, capacity, dcount, nullptr))) return rc;
-    if ((rc = download_pageable(count, dcount, sizeof(uint32_t), nullptr))) return rc;
-    const size_t n = std::min(*count, capacity);
-    if (n && (rc = download_pageable(keypoints, dkp, n * sizeof(zg_keypoint), nullptr))) return rc;
-    if (n && dde && (rc = download_pageable(descriptors, dde, n * sizeof(zg_binary_descriptor), nullptr))) return rc;
-    return ZG_OK;
+    if ((rc = download_counted(count, dcount, 1, keypoints, dkp, capacity)) || !dde) return rc;
+    return download_pageable(descriptors, dde, (size_t)std::min(*count, capacity) * sizeof(zg_binary_descriptor), nullptr);
 }
 
 int zg_orb_compute_host(const zg_image *src, const zg_orb_params *params, const zg_keypoint *keypoints, uint32_t n, zg_binary_descriptor *descriptors) {
@@ -698,12 +662,16 @@ int zg_orb_compute_host(const zg_image *src, const zg_orb_params *params, const 
     if (n == 0) return ZG_OK;
     HostStage in;
     if ((rc = in.upload(src, true, false))) return rc;
-    const size_t kp_b = align256((size_t)n * sizeof(zg_keypoint));
-    Scratch sc(nullptr);
-    if ((rc = scratch_alloc((void **)&sc.p, kp_b + (size_t)n * sizeof(zg_binary_descriptor), nullptr))) return rc;
-    if ((rc = upload_pageable(sc.p, keypoints, (size_t)n * sizeof(zg_keypoint), nullptr))) return rc;
-    if ((rc = compute(&in.dev, plan, (const zg_keypoint *)sc.p, n, (zg_binary_descriptor *)(sc.p + kp_b), nullptr))) return rc;
-    return download_pageable(descriptors, sc.p + kp_b, (size_t)n * sizeof(zg_binary_descriptor), nullptr);
+    // scratch: [keypoints][descriptors]
+    ScratchBlock sc;
+    zg_keypoint *dkp;
+    zg_binary_descriptor *dde;
+    sc.take(dkp, n);
+    sc.take(dde, n);
+    if ((rc = sc.alloc())) return rc;
+    if ((rc = upload_pageable(dkp, keypoints, (size_t)n * sizeof(zg_keypoint), nullptr))) return rc;
+    if ((rc = compute(&in.dev, plan, dkp, n, dde, nullptr))) return rc;
+    return download_pageable(descriptors, dde, (size_t)n * sizeof(zg_binary_descriptor), nullptr);
 }
 
 } // extern "C"

@@ -114,27 +114,25 @@ static int order_stat_impl(const zg_image *src, const zg_image *dst, uint32_t ra
     // in place: other workgroups would read pixels this one has already replaced
     const zg_image *in = src;
     zg_image copy{};
-    void *scratch = nullptr;
+    ScratchBlock scratch(s);
     const size_t ps = pixel_size(src->pixel);
     if (src->data == dst->data) {
-        if ((rc = scratch_alloc(&scratch, (size_t)src->rows * src->cols * ps, s))) return rc;
-        copy = zg_image{scratch, src->cols, src->rows, src->cols, src->pixel};
-        if ((rc = copy_impl(src, &copy, s))) { scratch_free(scratch, s); return rc; }
+        if ((rc = scratch.alloc((size_t)src->rows * src->cols * ps))) return rc;
+        copy = zg_image{scratch.p, src->cols, src->rows, src->cols, src->pixel};
+        if ((rc = copy_impl(src, &copy, s))) return rc;
         in = &copy;
     }
     const int tiles_x = (int)ceil_div(src->cols, 64), tiles_y = (int)ceil_div(src->rows, 4);
     const size_t lds = (size_t)pixel_channels(src->pixel) * (4 + 2 * radius) * (64 + 2 * radius);
-    rc = dispatch_pixel(src->pixel, [&](auto tag) -> int {
+    return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         if constexpr (!std::is_same<typename Px<PIX>::Elem, float>::value) {
             hipLaunchKernelGGL((k_order_stat<PIX>), dim3((unsigned)(tiles_x * tiles_y)), dim3(256), lds, s, dimg(in), dimg(dst), (int)radius, border, op, rank,
                                trim_each, tiles_x);
-            ZG_HIP(hipGetLastError());
+            if (const int e = launch_ok()) return e;
         }
         return ZG_OK;
     });
-    scratch_free(scratch, s);
-    return rc;
 }
 
 } // namespace zg

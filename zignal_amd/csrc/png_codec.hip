@@ -506,10 +506,11 @@ int decode_impl(const uint8_t *png, size_t len, const zg_png_limits *limits, con
     const int native = native_pixel(f);
     const bool direct = dst->pixel == native && dst_space == natural_space(native);
     const size_t native_bytes = direct ? 0 : (size_t)f.header.width * f.header.height * pixel_size(native);
-    uint8_t *dev = nullptr;
-    if ((rc = scratch_alloc((void **)&dev, L.total + 64 + native_bytes, s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc(L.total + 64 + native_bytes))) return rc;
+    uint8_t *dev = (uint8_t *)block.p;
     // the scan data is pageable host memory that dies with this call: a synchronised copy into scratch
-    if ((rc = upload_pageable(dev, scan.data(), L.total, s))) { scratch_free(dev, s); return rc; }
+    if ((rc = upload_pageable(dev, scan.data(), L.total, s))) return rc;
 
     UnpackArgs a{};
     for (int p = 0; p < 7; ++p) a.pass[p] = L.pass[p < L.npass ? p : 0];
@@ -537,10 +538,8 @@ int decode_impl(const uint8_t *png, size_t len, const zg_png_limits *limits, con
     case ZG_PIXEL_RGB_U8: hipLaunchKernelGGL((k_png_unpack<ZG_PIXEL_RGB_U8>), grid, dim3(256), 0, s, (const uint8_t *)dev, a, dimg(target)); break;
     default: hipLaunchKernelGGL((k_png_unpack<ZG_PIXEL_RGBA_U8>), grid, dim3(256), 0, s, (const uint8_t *)dev, a, dimg(target)); break;
     }
-    rc = hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
-    if (rc == ZG_OK && !direct) rc = zg_convert(&native_img, natural_space(native), dst, dst_space, nullptr, (zg_stream)s); // Image.convert (:1160-1184)
-    scratch_free(dev, s);
-    return rc;
+    if ((rc = launch_ok("k_png_copy_rows / k_png_unpack")) || direct) return rc;
+    return zg_convert(&native_img, natural_space(native), dst, dst_space, nullptr, (zg_stream)s); // Image.convert (:1160-1184)
 }
 
 // ---- device: pixels -> filtered scan data (png.zig:1535-1719) ----------------------------------------------------------------
@@ -684,7 +683,7 @@ template <int BPP> int filter_launch(const zg_image *src, int filter, uint8_t *f
     }
     hipLaunchKernelGGL((k_png_filter_rows<BPP>), dim3(ceil_div(ceil_div(n, 4), 256), src->rows), dim3(256), 0, s, dimg(src),
                        filter == ZG_PNG_FILTER_ADAPTIVE ? (const uint8_t *)choice : nullptr, filter, filtered);
-    return hipGetLastError() == hipSuccess ? ZG_OK : ZG_ERR_HIP;
+    return launch_ok("k_png_filter_rows");
 }
 int filter_impl(const zg_image *src, int filter, uint8_t *filtered, hipStream_t s) {
     int rc;
@@ -694,16 +693,14 @@ int filter_impl(const zg_image *src, int filter, uint8_t *filtered, hipStream_t 
     ZG_REQUIRE(filter >= ZG_PNG_FILTER_ADAPTIVE && filter <= 4, ZG_ERR_INVALID_ARGUMENT, "png filter: unknown filter %d", filter);
     ZG_REQUIRE(filtered != nullptr, ZG_ERR_INVALID_ARGUMENT, "png filter: null output");
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
-    uint8_t *work = nullptr; // per row: selectBestFilter's pick, then the filter the state machine settles on
-    if (filter == ZG_PNG_FILTER_ADAPTIVE && (rc = scratch_alloc((void **)&work, (size_t)src->rows * 2, s))) return rc;
-    uint8_t *best = work, *choice = work + src->rows;
+    ScratchBlock work(s); // per row: selectBestFilter's pick, then the filter the state machine settles on
+    if (filter == ZG_PNG_FILTER_ADAPTIVE && (rc = work.alloc((size_t)src->rows * 2))) return rc;
+    uint8_t *best = (uint8_t *)work.p, *choice = best + src->rows;
     switch (src->pixel) {
-    case ZG_PIXEL_U8: rc = filter_launch<1>(src, filter, filtered, best, choice, s); break;
-    case ZG_PIXEL_RGB_U8: rc = filter_launch<3>(src, filter, filtered, best, choice, s); break;
-    default: rc = filter_launch<4>(src, filter, filtered, best, choice, s); break;
+    case ZG_PIXEL_U8: return filter_launch<1>(src, filter, filtered, best, choice, s);
+    case ZG_PIXEL_RGB_U8: return filter_launch<3>(src, filter, filtered, best, choice, s);
+    default: return filter_launch<4>(src, filter, filtered, best, choice, s);
     }
-    if (work) scratch_free(work, s);
-    return rc;
 }
 
 // ---- the IDAT stream (png.zig:1297-1306 + std.compress.flate) -----------------------------------------------------------
@@ -827,8 +824,9 @@ int encode_impl(const zg_image *src, int src_space, const zg_png_encode_options 
     const int enc_pixel = direct ? src->pixel : ZG_PIXEL_RGB_U8; // any other T is converted to Rgb first (:1409-1423)
     const size_t row_bytes = (size_t)src->cols * pixel_size(enc_pixel), scan_bytes = (row_bytes + 1) * src->rows;
     const size_t rgb_bytes = direct ? 0 : (row_bytes * src->rows + 63) / 64 * 64;
-    uint8_t *dev = nullptr;
-    if ((rc = scratch_alloc((void **)&dev, rgb_bytes + scan_bytes, s))) return rc;
+    ScratchBlock block(s);
+    if ((rc = block.alloc(rgb_bytes + scan_bytes))) return rc;
+    uint8_t *dev = (uint8_t *)block.p;
     zg_image rgb{dev, src->cols, src->rows, src->cols, ZG_PIXEL_RGB_U8};
     if (!direct) rc = zg_convert(src, src_space, &rgb, ZG_CS_RGB, nullptr, (zg_stream)s);
     if (rc == ZG_OK) rc = filter_impl(direct ? src : &rgb, opt.filter, dev + rgb_bytes, s);
@@ -838,7 +836,7 @@ int encode_impl(const zg_image *src, int src_space, const zg_png_encode_options 
         scan.resize(scan_bytes);
         rc = download_pageable(scan.data(), dev + rgb_bytes, scan_bytes, s);
     }
-    scratch_free(dev, s);
+    block.reset(); // before the deflate on the host
     if (rc) return rc;
 
     std::vector<uint8_t> z;

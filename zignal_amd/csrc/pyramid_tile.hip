@@ -392,8 +392,7 @@ int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const floa
     }
     if (!J.n) return -1;
     hipLaunchKernelGGL(k_pyr_tile, dim3((unsigned)grid), dim3(PT_THREADS), 0, s, J);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 } // namespace zg

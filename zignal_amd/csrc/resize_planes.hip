@@ -426,8 +426,7 @@ int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint3
     }
     if (x4) { ZG_RB(4) } else { ZG_RB(1) }
 #undef ZG_RB
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 template <int PIX, int CLS, int KIND, int T>
@@ -441,8 +440,7 @@ static int launch_planes(const zg_image *src, const zg_image *dst, const AxisTab
     if (n > MAX_FRAMES_PER_LAUNCH) return -1;
     hipLaunchKernelGGL((k_resize_planes<PIX, CLS, KIND, T>), dim3((unsigned)(tiles_x * tiles_y), n), dim3(256), 0, s, dimg(src), dimg(dst), tx, ty,
                        ratio_x, ratio_y, tiles_x, fr);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 template <int PIX>
@@ -500,16 +498,14 @@ int resize_lanczos_weights_impl(const zg_image *src, const zg_image *dst, const 
     build_axis(ZG_INTERP_LANCZOS, src->rows, dst->rows, 6, iy, own);
     std::memcpy(host.data() + 2 * nx, iy.data(), ny * 4);
     std::memcpy(host.data() + 2 * nx + ny, wy ? (const void *)wy : (const void *)own.data(), ny * 4);
-    int32_t *dev = nullptr;
+    ScratchBlock block(s);
     int rc;
-    if ((rc = scratch_alloc((void **)&dev, host.size() * 4, s))) return rc;
-    if ((rc = upload_pageable(dev, host.data(), host.size() * 4, s)) == ZG_OK) {
-        const AxisTable tx{dev, dev + nx}, ty{dev + 2 * nx, dev + 2 * nx + ny};
-        rc = src->pixel == ZG_PIXEL_RGB_U8 ? resize_planes_pix<ZG_PIXEL_RGB_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s)
-                                           : resize_planes_pix<ZG_PIXEL_RGBA_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s);
-    }
-    scratch_free(dev, s);
-    return rc;
+    if ((rc = block.alloc(host.size() * 4))) return rc;
+    int32_t *dev = (int32_t *)block.p;
+    if ((rc = upload_pageable(dev, host.data(), host.size() * 4, s))) return rc;
+    const AxisTable tx{dev, dev + nx}, ty{dev + 2 * nx, dev + 2 * nx + ny};
+    return src->pixel == ZG_PIXEL_RGB_U8 ? resize_planes_pix<ZG_PIXEL_RGB_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s)
+                                         : resize_planes_pix<ZG_PIXEL_RGBA_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s);
 }
 
 } // namespace zg

@@ -217,8 +217,7 @@ static int launch_sobel_stream(const zg_image *src, const zg_image *dst, uint32_
     const uint64_t items = (uint64_t)a.strips_x * a.strips_y;
     if (items > 0x7fffffffu || n > MAX_FRAMES_PER_LAUNCH) return -1;
     hipLaunchKernelGGL((k_sobel_stream<SP, 1>), dim3((unsigned)items, n), dim3(64), 0, s, a);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
+    return launch_ok();
 }
 
 // Returns -1 when the preconditions do not hold (the caller runs k_sobel).

@@ -11,6 +11,7 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/zignal_hip.h"
 
@@ -35,6 +36,15 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
             return (status);               \
         }                                  \
     } while (0)
+
+// After a kernel launch: the launch's error, if any, reported through hip_fail with `what` and the caller's file and line. `what` is
+// part of the message, which callers may match on: sites written before this helper keep the text they always reported, the
+// expression of their ZG_HIP(...) check ("hipGetLastError()", the default, or "e" / "launch_error" where the error was first saved
+// in a variable of that name); newer sites name the kernel.
+inline int launch_ok(const char *what = "hipGetLastError()", const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ZG_OK : hip_fail(e, what, file, line);
+}
 
 inline hipStream_t as_stream(zg_stream s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -181,12 +191,57 @@ constexpr unsigned GRID_Y_MAX = 65535u;
 inline dim3 row_grid(unsigned gx, unsigned rows) { return rows <= GRID_Y_MAX ? dim3(gx, rows, 1) : dim3(gx, GRID_Y_MAX, ceil_div(rows, GRID_Y_MAX)); }
 __device__ inline int grid_row() { return (int)(blockIdx.z * GRID_Y_MAX + blockIdx.y); }
 
+// ---- scratch -------------------------------------------------------------------------------
+// scratch blocks from the library's caching allocator, ordered on stream s (zg_runtime.cpp)
+int scratch_alloc(void **out, size_t bytes, hipStream_t s);
+void scratch_free(void *p, hipStream_t s);
+size_t scratch_block_budget(); // bytes one long-lived scratch block may take so that a few of them stay cached (a quarter of the cache limit)
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// The owner of one scratch block: taken on the stream given at construction, given back on it by reset() or the destructor, whichever
+// way the function is left. A block of several parts: take(pointer, count) for each part in layout order, then alloc() — a part is
+// count * sizeof(T) bytes rounded up to 256, the block is their sum, and alloc() sets the pointers. take() keeps the pointer's
+// address: the pointer (a local, or a member of an object that neither moves nor dies) must stay where it is until alloc() returns.
+struct ScratchBlock {
+    char *p = nullptr;
+    explicit ScratchBlock(hipStream_t stream = nullptr) : s(stream) {}
+    ScratchBlock(const ScratchBlock &) = delete;
+    ScratchBlock &operator=(const ScratchBlock &) = delete;
+    ~ScratchBlock() { reset(); }
+    int alloc(size_t bytes) {
+        reset();
+        return scratch_alloc((void **)&p, bytes, s);
+    }
+    void reset() {
+        scratch_free(p, s);
+        p = nullptr;
+    }
+    template <typename T> void take(T *&part, size_t count) {
+        parts.push_back(Part{(void **)&part, planned});
+        planned += align256(count * sizeof(T));
+    }
+    int alloc() {
+        if (const int rc = alloc(planned)) return rc;
+        for (const Part &part : parts) *part.pointer = p + part.offset;
+        return ZG_OK;
+    }
+
+private:
+    struct Part {
+        void **pointer;
+        size_t offset;
+    };
+    hipStream_t s;
+    std::vector<Part> parts;
+    size_t planned = 0;
+};
+
 // Host-layer scaffolding (zg_runtime.cpp): stage host images to the device, run, copy back.
 struct HostStage {
-    zg_image dev{};       // device twin (contiguous: stride == cols)
+    zg_image dev{};       // device twin (contiguous: stride == cols), in `block`
+    ScratchBlock block;
     const zg_image *host{};
     bool writeback = false;
-    ~HostStage();
     int upload(const zg_image *h, bool copy_in, bool write_back);
     int finish();         // D2H if writeback
 };
@@ -226,6 +281,13 @@ int upload_pageable_rows(void *dst_dev, const void *src_host, size_t spitch, siz
 // the reverse trips: device memory (contiguous) into pageable host memory / into host rows `dpitch` apart
 int download_pageable(void *dst_host, const void *src_dev, size_t bytes, hipStream_t s);
 int download_pageable_rows(void *dst_host, size_t dpitch, const void *src_dev, size_t width, size_t rows, hipStream_t s);
+// The host tail of a counted list: `words` count words come back, the last of them the list's length, then the first
+// min(length, capacity) entries of the list.
+template <typename T> int download_counted(uint32_t *counts, const uint32_t *counts_dev, uint32_t words, T *list, const void *list_dev, uint32_t capacity) {
+    if (const int rc = download_pageable(counts, counts_dev, words * sizeof(uint32_t), nullptr)) return rc;
+    const size_t n = counts[words - 1] < capacity ? counts[words - 1] : capacity;
+    return download_pageable(list, list_dev, n * sizeof(T), nullptr);
+}
 
 // Frames of a batch inside one launch: bytes from one frame to the next on both sides. The frame index is blockIdx.y (grids are
 // tiles-per-frame x frames), so a one-image launch pays nothing for it: round 3 carried the index in blockIdx.x and every workgroup
@@ -236,11 +298,7 @@ struct FrameSpan {
 };
 constexpr uint32_t MAX_FRAMES_PER_LAUNCH = 65535; // gridDim.y
 
-// scratch blocks from the library's caching allocator, ordered on stream s (zg_runtime.cpp)
-int scratch_alloc(void **out, size_t bytes, hipStream_t s);
 int host_threads(); // ZIGNAL_HIP_HOST_THREADS, else min(16, hardware threads)
-void scratch_free(void *p, hipStream_t s);
-size_t scratch_block_budget(); // bytes one long-lived scratch block may take so that a few of them stay cached (a quarter of the cache limit)
 
 // Graph capture (zg_runtime.cpp). capturing(s): `s` is recording a capture right now. refuse_under_capture: what a call that cannot be
 // recorded (a synchronous upload of short-lived host memory, a value read back to the host, a first-use table) calls before it enqueues

@@ -364,10 +364,6 @@ int download_pageable(void *dst_host, const void *src_dev, size_t bytes, hipStre
 }
 
 // The device twin of a host image comes from the scratch cache: a second call of the same size pays no allocation.
-HostStage::~HostStage() {
-    if (dev.data) scratch_free(dev.data, nullptr);
-}
-
 int HostStage::upload(const zg_image *h, bool copy_in, bool write_back) {
     int rc = check_image(h, "host image", false);
     if (rc) return rc;
@@ -379,7 +375,8 @@ int HostStage::upload(const zg_image *h, bool copy_in, bool write_back) {
     const size_t ps = pixel_size(h->pixel);
     const size_t bytes = (size_t)h->rows * h->cols * ps;
     if (bytes == 0) return ZG_OK;
-    if ((rc = scratch_alloc(&dev.data, bytes, nullptr))) return rc;
+    if ((rc = block.alloc(bytes))) return rc;
+    dev.data = block.p;
     if (copy_in) {
         if ((rc = upload_pageable_rows(dev.data, h->data, h->stride * ps, (size_t)h->cols * ps, h->rows, nullptr))) return rc;
     }
