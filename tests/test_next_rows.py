@@ -140,9 +140,12 @@ def test_pyramid_parity(oracle, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", ((33, 256), (31, 272), (32, 256), (64, 1040), (95, 1024), (500, 2064), (1080, 1920), (20, 640)))
 def test_pyramid_u8_fused_levels(oracle, shape):
-    """Image(u8) levels come from k_pyr_tile (reductions from 1.3 on whose taps fit, pyramid_tile.hip) and the others from the multi-job kernels
-    (k_rows_u8f_multi, then k_cols_bilinear_u8_multi: the column pass evaluated at the resize's taps, 31-row bands): band seams, the anchored last
-    band, planes shorter than a band, mirrored right / bottom taps, scale 1 (a blurred copy) and both band-loop forms (inside / edge)."""
+    """Image(u8) levels come from the tile kernel, k_pyr_tile (pyramid_tile.hip: blur and bilinear resize of one tile in LDS, every level reduced by
+    1.3 to 3.9 whose taps fit, up to 8 jobs). Round 5's route is the fallback for what the tile kernel leaves (ratios below 1.3 or from 3.9, longer
+    taps, more jobs, unaligned sources; all levels with ZIGNAL_HIP_NO_PYRAMID_TILE set): try_pyramid_levels_u8 with the multi-job kernels
+    k_rows_u8f_multi, then k_cols_bilinear_u8_multi (the column pass evaluated at the resize's taps, 31-row bands). The shapes cover tile and band
+    seams, the anchored last band, planes shorter than a band, mirrored right / bottom taps, scale 1 (a blurred copy) and both band-loop forms
+    (inside / edge); the scale factors put levels on both routes (1.05 and 1.2 below the tile kernel's ratio, 1.5 to 2.1 inside it)."""
     src = oracle.synth_u8(90 + shape[0], shape)
     for n, sf, sigma in ((4, 1.2, 1.6), (6, 1.5, 1.0), (3, 1.05, 0.8), (3, 2.0, 3.0), (3, 2.1, 2.91), (9, 1.2, 1.6)):
         want = oracle.pyramid(src, n, sf, sigma)
@@ -155,6 +158,10 @@ def test_pyramid_u8_fused_levels(oracle, shape):
 
 @pytest.mark.gpu
 def test_pyramid_u8_fused_levels_full_size_and_views(oracle):
+    """The default pyramid (8 levels, 1.2, 1.6) of a 2048 x 4096 Image(u8): levels reduced by 1.3 and more come from the tile kernel (k_pyr_tile),
+    the first level (1.2) from round 5's fallback route (k_rows_u8f_multi + k_cols_bilinear_u8_multi). Then two source views: one whose pitch is
+    not its width, which the tile kernel takes, and one that starts at an odd column, which it refuses (pyramid_tile.hip: origin & 3) and the
+    fallback builds."""
     src = oracle.synth_u8(93, (2048, 4096))
     want = oracle.pyramid(src, 8, 1.2, 1.6)
     pyr = zg.ImagePyramid.build_default(dev(src))

@@ -157,9 +157,9 @@ static void morph_chain(const zg_image *src, const zg_image *dst, const MorphKer
     const zg_image *cur = src;
     for (uint32_t i = 0; i < iterations; ++i) {
         const bool last = i + 1 == iterations;
-        // the last step writes dst; if dst is the buffer being read (in-place, single step) go through scratch first
+        // the last step writes dst; if dst shares bytes with the buffer being read (in place or a shifted view of it, single step) go through scratch first
         const zg_image *out = last ? dst : (cur == &a ? &b : &a);
-        if (last && cur->data == dst->data) {
+        if (last && spans_overlap(cur, dst)) {
             launch_morph(cur, &a, k, erode, s);
             (void)copy_impl(&a, dst, s);
         } else {

@@ -740,9 +740,7 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
     const int C = pixel_channels(src->pixel);
     if (n == 1 && !pixel_is_float(src->pixel) && radius <= 7 && (uint64_t)src->rows * src->cols * 255u < (1u << 24)) {
         // the in-place call (examples/src/face_alignment.zig:95) keeps the integral-image route: there every output is written after every input is read
-        const char *sb = (const char *)src->data, *se = sb + ((size_t)(src->rows - 1) * src->stride + src->cols) * pixel_size(src->pixel);
-        const char *db = (const char *)dst->data, *de = db + ((size_t)(dst->rows - 1) * dst->stride + dst->cols) * pixel_size(dst->pixel);
-        if (se <= db || de <= sb) {
+        if (!spans_overlap(src, dst)) {
             const dim3 grid(ceil_div(dst->cols, 64), ceil_div(dst->rows, 4));
             return dispatch_pixel(src->pixel, [&](auto tag) -> int {
                 constexpr int PIX = decltype(tag)::value;
@@ -757,6 +755,18 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
     }
     // u8 planes and Rgba(u8), radius 1..3: the SAT stays in LDS (box_fused.hip)
     if ((rc = try_box_fused(src, dst, n, src_frame, dst_frame, radius, sharpen, s)) >= 0) return rc;
+    // sharpen reads the original pixel beside the SAT when it writes (k_box_mean): in place every lane reads the pixel it then writes, but into
+    // a destination view that shares bytes with the source at another offset, lanes would read what others have written. The source is copied first.
+    // One image only: a batch (n > 1) comes from the pipeline, whose source and destination frames are separate buffers; other callers of the
+    // frames entry must keep theirs disjoint.
+    zg_image aside{};
+    ScratchBlock aside_block(s);
+    if (sharpen && n == 1 && spans_overlap(src, dst) && (src->data != dst->data || src->stride != dst->stride)) {
+        if ((rc = aside_block.alloc((size_t)src->rows * src->cols * pixel_size(src->pixel)))) return rc;
+        aside = zg_image{aside_block.p, src->cols, src->rows, src->cols, src->pixel};
+        if ((rc = copy_impl(src, &aside, s))) return rc;
+        src = &aside;
+    }
     const size_t plane = sat_plane_stride(src, sat_fused_applies(src, false));
     const size_t sat_frame = (size_t)C * plane; // elements
     const bool buf = sat_frame * sizeof(float) < (1ull << 32);

@@ -863,10 +863,8 @@ int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t s
     const size_t kbytes = (size_t)n * src->rows * nk * C * sizeof(float);
     // the in-place call (examples/src/face_alignment.zig:95): a strip's outputs would be read by its neighbours' chains, so the source is copied first
     const size_t px = pixel_size(src->pixel);
-    const char *sb = (const char *)src->data, *se = sb + (size_t)(n - 1) * src_frame + ((size_t)(src->rows - 1) * src->stride + src->cols) * px;
-    const char *db = (const char *)dst->data, *de = db + (size_t)(n - 1) * dst_frame + ((size_t)(dst->rows - 1) * dst->stride + dst->cols) * px;
     // dword loads: a source whose rows do not start on dwords is copied too (a view of a grey image at an odd column)
-    const bool overlap = !(se <= db || de <= sb) || ((uintptr_t)src->data & 3) != 0 || ((size_t)src->stride * C) % 4 != 0 || (src_frame % 4) != 0;
+    const bool overlap = spans_overlap(src, dst, n, src_frame, dst_frame) || ((uintptr_t)src->data & 3) != 0 || ((size_t)src->stride * C) % 4 != 0 || (src_frame % 4) != 0;
     // 32-bit offsets inside a frame's rows and carries
     if ((size_t)src->rows * (overlap ? (size_t)src->cols + 3 : (size_t)src->stride) * C + 64 >= (1ull << 32) || (size_t)src->rows * nk * C * sizeof(float) >= (1ull << 32)) return -1;
     zg_image from = *src;

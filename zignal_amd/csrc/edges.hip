@@ -100,6 +100,17 @@ static int sobel_impl(const zg_image *src, const zg_image *dst, hipStream_t s, u
                src->rows, src->cols, dst->rows, dst->cols);
     ZG_REQUIRE(dst->pixel == ZG_PIXEL_U8, ZG_ERR_INVALID_ARGUMENT, "sobel: the output is Image(u8)");
     if (src->rows == 0 || src->cols == 0) return ZG_OK;
+    // in place on an Image(u8), or a destination view that shares bytes with the source: a lane reads its neighbours' pixels, so the source is copied first.
+    // One image only: a batch (n > 1, sobel_frames) comes from the pipeline, whose source and destination frames are separate buffers; other
+    // callers of the frames entry must keep theirs disjoint.
+    zg_image copy{};
+    ScratchBlock aside(s);
+    if (n == 1 && spans_overlap(src, dst)) {
+        if ((rc = aside.alloc((size_t)src->rows * src->cols * pixel_size(src->pixel)))) return rc;
+        copy = zg_image{aside.p, src->cols, src->rows, src->cols, src->pixel};
+        if ((rc = copy_impl(src, &copy, s))) return rc;
+        src = &copy;
+    }
     if (const int rcs = try_sobel_stream(src, dst, n, src_frame, dst_frame, s); rcs >= 0) return rcs; // u8 / Rgba(u8): one wave per column strip
     const int tiles_x = (int)ceil_div(src->cols, 64), tiles_y = (int)ceil_div(src->rows, 16);
     if (n > MAX_FRAMES_PER_LAUNCH) return -1; // the caller goes frame by frame

@@ -111,12 +111,12 @@ static int order_stat_impl(const zg_image *src, const zg_image *dst, uint32_t ra
         const long long trimmed_each = (long long)std::trunc(std::floor(param * (double)area));
         trim_each = (int)std::min<long long>(trimmed_each, area / 2);
     }
-    // in place: other workgroups would read pixels this one has already replaced
+    // in place, or a destination view that shares bytes with the source: other workgroups would read pixels this one has already replaced
     const zg_image *in = src;
     zg_image copy{};
     ScratchBlock scratch(s);
     const size_t ps = pixel_size(src->pixel);
-    if (src->data == dst->data) {
+    if (spans_overlap(src, dst)) {
         if ((rc = scratch.alloc((size_t)src->rows * src->cols * ps))) return rc;
         copy = zg_image{scratch.p, src->cols, src->rows, src->cols, src->pixel};
         if ((rc = copy_impl(src, &copy, s))) return rc;

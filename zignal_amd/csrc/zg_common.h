@@ -73,6 +73,17 @@ struct DImg {
 inline DImg dimg(const zg_image *im) {
     return DImg{im->data, (uint64_t)im->stride, (int32_t)im->rows, (int32_t)im->cols};
 }
+// Do the byte spans of two views (of n frames each, a_frame / b_frame bytes apart) share a byte? The in-place call, and two views of one frame
+// whose rows interleave: a kernel that reads neighbours of the pixel it writes must then read a copy of the source. The one definition of
+// the test (box_blur.hip, box_fused.hip, binary.hip, order_stat.hip, edges.hip, the host band layer). It compares the bounding spans, first
+// byte to last, not the rectangles: two disjoint rectangles side by side in one frame count as overlapping, which costs such a call a copy
+// it would not need and never a wrong pixel.
+inline bool spans_overlap(const zg_image *a, const zg_image *b, uint32_t n = 1, size_t a_frame = 0, size_t b_frame = 0) {
+    if (a->rows == 0 || a->cols == 0 || b->rows == 0 || b->cols == 0 || n == 0) return false;
+    const uintptr_t a0 = (uintptr_t)a->data, a1 = a0 + (size_t)(n - 1) * a_frame + ((size_t)(a->rows - 1) * a->stride + a->cols) * pixel_size(a->pixel);
+    const uintptr_t b0 = (uintptr_t)b->data, b1 = b0 + (size_t)(n - 1) * b_frame + ((size_t)(b->rows - 1) * b->stride + b->cols) * pixel_size(b->pixel);
+    return a0 < b1 && b0 < a1;
+}
 
 // Compile-time pixel traits. `Vec` is the register / LDS form of one pixel (a clang ext vector, so
 // it lives in VGPRs and moves with one instruction); 3-channel pixels pad to 4 lanes in registers

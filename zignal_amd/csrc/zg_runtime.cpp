@@ -435,11 +435,8 @@ int host_banded(const zg_image *src, const zg_image *dst, uint32_t halo, const B
     const size_t row_s = (size_t)src->cols * ps_s, row_d = (size_t)dst->cols * ps_d;
     const size_t bytes_s = row_s * src->rows, bytes_d = row_d * dst->rows;
     if (bytes_s + bytes_d < ((size_t)24 << 20)) return -1; // small frames: one trip each way is as good
-    { // an in-place call (or any overlap) would have later bands read rows that earlier bands already overwrote
-        const uintptr_t s0 = (uintptr_t)src->data, s1 = s0 + ((size_t)(src->rows - 1) * src->stride + src->cols) * ps_s;
-        const uintptr_t d0 = (uintptr_t)dst->data, d1 = d0 + ((size_t)(dst->rows - 1) * dst->stride + dst->cols) * ps_d;
-        if (s0 < d1 && d0 < s1) return -1;
-    }
+    // an in-place call (or any overlap) would have later bands read rows that earlier bands already overwrote
+    if (spans_overlap(src, dst)) return -1;
     const uint32_t rows = src->rows, min_band = halo > 0 ? 2 * halo : 1;
     size_t band_mib = 16; // ~16 MiB of the larger side per band
     if (const char *e = getenv("ZIGNAL_HIP_BAND_MIB")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 1024) band_mib = (size_t)v; }
