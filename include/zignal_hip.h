@@ -737,4 +737,8 @@ ZG_API void zg_jpeg_free(void *p);
 /* Image(T).floodFill (src/image/flood_fill.zig): a module of its own in the same way (_FLOOD_SIGNATURES, zig/zignal_hip_flood.zig). */
 #include "zignal_hip_flood.h"
 
+/* Image(T).psnr, ssim and meanPixelError (src/image/metrics.zig) and the exact sequential f64 sum under them: a module of its own in the
+ * same way (_METRICS_SIGNATURES, zig/zignal_hip_metrics.zig). */
+#include "zignal_hip_metrics.h"
+
 #endif /* ZIGNAL_HIP_H */

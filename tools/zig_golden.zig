@@ -34,6 +34,9 @@
 //!                           in both directions: every case carries its pixels as bytes, the seed, the options (the threshold as f64
 //!                           bits, the exact square root of a sum of squares and the f64 below it among them), the fill value and the
 //!                           filled image   src/image/flood_fill.zig:28-131
+//!   metrics                 generateSsimWindow's 121 f64 weights at comptime and at run time (u64 bit patterns), @exp of an f64 at the
+//!                           window's 20 distinct arguments and std.math.log10 of an f64 on a sweep of mse-like values, as [input
+//!                           bits, output bits]: what zg_ssim_window_host and zg_psnr_from_mse restate   src/image/metrics.zig:53, 230-249
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
@@ -440,6 +443,67 @@ fn floodSection(w: anytype, allocator: std.mem.Allocator) !void {
     try w.print("\n  ],\n", .{});
 }
 
+// ---- metrics: the host arithmetic of psnr and ssim in f64 -----------------------------------------------------------------------------
+fn runtime64(x: f64) f64 {
+    var v = x;
+    std.mem.doNotOptimizeAway(&v);
+    return v;
+}
+
+/// src/image/metrics.zig:230-249; `at_runtime` keeps the compiler from folding the exponentials
+fn ssimWindow(at_runtime: bool) [121]f64 {
+    const sigma: f64 = 1.5;
+    var window: [121]f64 = undefined;
+    var sum: f64 = 0.0;
+    for (0..11) |dy| {
+        for (0..11) |dx| {
+            const y: f64 = @as(f64, @floatFromInt(dy)) - 5.0;
+            const x: f64 = @as(f64, @floatFromInt(dx)) - 5.0;
+            const arg = -(x * x + y * y) / (2.0 * sigma * sigma);
+            const gauss = @exp(if (at_runtime) runtime64(arg) else arg);
+            window[dy * 11 + dx] = gauss;
+            sum += gauss;
+        }
+    }
+    for (&window) |*v| v.* /= sum;
+    return window;
+}
+
+const ssim_window_comptime = blk: {
+    @setEvalBranchQuota(20000);
+    break :blk ssimWindow(false);
+};
+
+fn metricsSection(w: anytype) !void {
+    try w.print("  \"metrics\": {{\"ssim_window_comptime\": [", .{});
+    for (ssim_window_comptime, 0..) |v, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", @as(u64, @bitCast(v)) });
+    try w.print("], \"ssim_window_runtime\": [", .{});
+    for (ssimWindow(true), 0..) |v, i| try w.print("{s}{d}", .{ if (i == 0) "" else ",", @as(u64, @bitCast(v)) });
+    try w.print("], \"exp\": [", .{});
+    var first = true;
+    for (0..6) |yi| for (yi..6) |xi| {
+        const x: f64 = @floatFromInt(xi);
+        const y: f64 = @floatFromInt(yi);
+        const arg = runtime64(-(x * x + y * y) / (2.0 * 1.5 * 1.5));
+        try w.print("{s}[{d},{d}]", .{ if (first) "" else ",", @as(u64, @bitCast(arg)), @as(u64, @bitCast(@exp(arg))) });
+        first = false;
+    };
+    try w.print("], \"log10\": [", .{});
+    var rng = Lcg{ .s = 91 };
+    for (0..4096) |i| {
+        // mse-like values from 1e-12 to 65025, the component maxima, and values around 1
+        const u = @as(f64, @floatFromInt(rng.next() >> 8)) / 16777216.0;
+        const x = runtime64(switch (i % 4) {
+            0 => 65025.0 * u,
+            1 => std.math.pow(f64, 10.0, -12.0 + 17.0 * u),
+            2 => 0.5 + 1.5 * u,
+            else => if (i == 3) 255.0 else if (i == 7) 1.0 else 255.0 * u,
+        });
+        try w.print("{s}[{d},{d}]", .{ if (i == 0) "" else ",", @as(u64, @bitCast(x)), @as(u64, @bitCast(std.math.log10(x))) });
+    }
+    try w.print("]}},\n", .{});
+}
+
 pub fn main(init: std.process.Init) !void {
     var buffer: [1 << 16]u8 = undefined;
     var stdout = std.Io.File.stdout().writer(init.io, &buffer);
@@ -536,6 +600,9 @@ pub fn main(init: std.process.Init) !void {
 
     // src/image/flood_fill.zig:28-131 through the zignal module
     try floodSection(w, init.gpa);
+
+    // src/image/metrics.zig:53, 230-249
+    try metricsSection(w);
 
     // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
     // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])

@@ -135,6 +135,16 @@ class ZgFloodFillOptions(C.Structure):
 FLOOD_MODE_SEED, FLOOD_MODE_NEIGHBOR = range(2)
 
 
+class ZgMetricResult(C.Structure):
+    """zg_metric_result: the left-to-right f64 sum, the number of terms, the metric's value and how many terms were added serially."""
+    _fields_ = [("sum", C.c_double), ("count", C.c_uint64), ("value", C.c_double), ("serial_terms", C.c_uint64)]
+
+
+class ZgMetricOptions(C.Structure):
+    """zg_metric_options: the caller's 121 SSIM weights (host memory) and the SSIM map to fill, both optional."""
+    _fields_ = [("ssim_window", C.c_void_p), ("ssim_map", C.c_void_p)]
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -382,6 +392,26 @@ _FLOOD_SIGNATURES = {
 _FLOOD_RESTYPES = {"zg_flood_fill_tile": C.c_uint32}
 FLOOD_EXPORTED_SYMBOLS = tuple(_FLOOD_SIGNATURES)
 
+# the metrics module: every symbol include/zignal_hip_metrics.h declares
+_F64P = C.POINTER(C.c_double)
+_METRIC_OPT = C.POINTER(ZgMetricOptions)
+_METRICS_SIGNATURES = {
+    "zg_sum_f64_chunk": [],
+    "zg_ssim_window_host": [_F64P],
+    "zg_psnr_from_mse": [C.c_double, C.c_double],
+    "zg_exp_f64_host": [C.c_double],
+    "zg_log10_f64_host": [C.c_double],
+    "zg_sum_f64_sequential": [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_psnr": [_IMG, _IMG, _METRIC_OPT, C.c_void_p, C.c_void_p],
+    "zg_mean_pixel_error": [_IMG, _IMG, _METRIC_OPT, C.c_void_p, C.c_void_p],
+    "zg_ssim": [_IMG, _IMG, _METRIC_OPT, C.c_void_p, C.c_void_p],
+    "zg_psnr_host": [_IMG, _IMG, _METRIC_OPT, _F64P, C.POINTER(ZgMetricResult)],
+    "zg_mean_pixel_error_host": [_IMG, _IMG, _METRIC_OPT, _F64P, C.POINTER(ZgMetricResult)],
+    "zg_ssim_host": [_IMG, _IMG, _METRIC_OPT, _F64P, C.POINTER(ZgMetricResult)],
+}
+_METRICS_RESTYPES = {"zg_sum_f64_chunk": C.c_uint32, "zg_psnr_from_mse": C.c_double, "zg_exp_f64_host": C.c_double, "zg_log10_f64_host": C.c_double}
+METRICS_EXPORTED_SYMBOLS = tuple(_METRICS_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -392,7 +422,7 @@ def lib() -> C.CDLL:
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
-                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES)):
+                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

@@ -120,6 +120,31 @@ template <template <typename> class Img, typename T> class Ops {
         if constexpr (Derived::on_device) check(dev(a..., self().stream()));
         else check(host(a...));
     }
+    // psnr, meanPixelError and ssim: see the public methods
+    template <class DevFn, class HostFn>
+    double metric(DevFn dev, HostFn host, const Derived &other, const zg_metric_options &opt, zg_metric_result *result_device, bool is_psnr) const {
+        const zg_image a = desc(), b = other.desc();
+        double value = 0;
+        if constexpr (Derived::on_device) {
+            if (result_device) {
+                check(dev(&a, &b, &opt, result_device, self().stream()));
+                return 0;
+            }
+            void *mem = nullptr;
+            check(zg_malloc(&mem, sizeof(zg_metric_result)));
+            zg_metric_result r{};
+            int rc = dev(&a, &b, &opt, (zg_metric_result *)mem, self().stream());
+            if (rc == ZG_OK) rc = zg_memcpy_d2h(&r, mem, sizeof r, self().stream()); // waits for the stream
+            zg_free(mem);
+            check(rc);
+            value = is_psnr ? zg_psnr_from_mse(r.value, PixelTraits<T>::pixel == ZG_PIXEL_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGB_U8 ||
+                                                                PixelTraits<T>::pixel == ZG_PIXEL_RGBA_U8 ? 255.0 : 1.0)
+                            : r.value;
+        } else {
+            check(host(&a, &b, &opt, &value, (zg_metric_result *)nullptr));
+        }
+        return value;
+    }
 
   public:
     uint32_t rows = 0, cols = 0;
@@ -255,6 +280,21 @@ template <template <typename> class Img, typename T> class Ops {
         if constexpr (Derived::on_device) check(zg_flood_fill(&s, row, col, seed_device, (const void *)&fill_value, &o, filled_count_device, self().stream()));
         else check(zg_flood_fill_host(&s, row, col, (const void *)&fill_value, &o, &filled));
         return filled;
+    }
+    // ---- metrics (metrics.zig:10-54 psnr, :56-112 ssim, :114-166 meanPixelError) ----
+    // An Image is measured synchronously and the method's f64 returned. A DeviceImage's metric is enqueued on stream(): with
+    // result_device (a device zg_metric_result: value is the mse for psnr, the method's value otherwise) nothing waits and 0 is returned;
+    // without it the call waits for the stream and returns the value. ssim_map, when not null, is (rows - 10) x (cols - 10) f64 on the
+    // image's side; window, when not null, 121 host weights in place of the library's. A shape mismatch throws DimensionMismatch, an
+    // image below 11 x 11 InvalidArgument (error.ImageTooSmall).
+    double psnr(const Derived &other, zg_metric_result *result_device = nullptr) const {
+        return metric(zg_psnr, zg_psnr_host, other, zg_metric_options{nullptr, nullptr}, result_device, true);
+    }
+    double meanPixelError(const Derived &other, zg_metric_result *result_device = nullptr) const {
+        return metric(zg_mean_pixel_error, zg_mean_pixel_error_host, other, zg_metric_options{nullptr, nullptr}, result_device, false);
+    }
+    double ssim(const Derived &other, zg_metric_result *result_device = nullptr, double *ssim_map = nullptr, const double *window = nullptr) const {
+        return metric(zg_ssim, zg_ssim_host, other, zg_metric_options{window, ssim_map}, result_device, false);
     }
     void flipLeftRight() const { const zg_image s = desc(); run(zg_flip_left_right, zg_flip_left_right_host, &s); }   // transforms.zig:28
     void flipTopBottom() const { const zg_image s = desc(); run(zg_flip_top_bottom, zg_flip_top_bottom_host, &s); }   // transforms.zig:36

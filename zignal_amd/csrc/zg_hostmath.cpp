@@ -297,4 +297,95 @@ double sin_f64(double x) {
     }
 }
 
+// ---- Zig's f64 exp and log10 (its ports of musl's exp.c, the FreeBSD e_exp.c form, and log10.c) ----
+namespace {
+double from_words(uint32_t hi, uint32_t lo) {
+    const uint64_t u = (uint64_t)hi << 32 | lo;
+    double d;
+    std::memcpy(&d, &u, 8);
+    return d;
+}
+uint32_t low_word(double x) {
+    uint64_t u;
+    std::memcpy(&u, &x, 8);
+    return (uint32_t)u;
+}
+double scalbn_f64(double x, int n) {
+    double y = x;
+    if (n > 1023) {
+        y *= 0x1p1023; n -= 1023;
+        if (n > 1023) { y *= 0x1p1023; n -= 1023; if (n > 1023) n = 1023; }
+    } else if (n < -1022) {
+        y *= 0x1p-1022 * 0x1p53; n += 1022 - 53;
+        if (n < -1022) { y *= 0x1p-1022 * 0x1p53; n += 1022 - 53; if (n < -1022) n = -1022; }
+    }
+    return y * from_words((uint32_t)(0x3ff + n) << 20, 0);
+}
+} // namespace
+
+double exp_f64(double x) {
+    const double ln2hi = 6.93147180369123816490e-01, ln2lo = 1.90821492927058770002e-10, invln2 = 1.44269504088896338700e+00;
+    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
+                 P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+    uint32_t hx = high_word(x);
+    const int sign = (int)(hx >> 31);
+    hx &= 0x7fffffff;
+    if (hx >= 0x4086232b) { // |x| >= 708.39
+        if (x != x) return x;
+        if (x > 709.782712893383973096) return x * 0x1p1023;
+        if (x < -708.39641853226410622 && x < -745.13321910194110842) return 0;
+    }
+    double hi, lo;
+    int k;
+    if (hx > 0x3fd62e42) { // |x| > 0.5 ln2
+        if (hx >= 0x3ff0a2b2) k = (int)(invln2 * x + (sign ? -0.5 : 0.5)); // |x| >= 1.5 ln2
+        else k = 1 - sign - sign;
+        hi = x - (double)k * ln2hi; // exact
+        lo = (double)k * ln2lo;
+        x = hi - lo;
+    } else if (hx > 0x3e300000) { // |x| > 2^-28
+        k = 0; hi = x; lo = 0;
+    } else {
+        return 1 + x;
+    }
+    const double xx = x * x;
+    const double c = x - xx * (P1 + xx * (P2 + xx * (P3 + xx * (P4 + xx * P5))));
+    const double y = 1 + (x * c / (2 - c) - lo + hi);
+    return k == 0 ? y : scalbn_f64(y, k);
+}
+
+double log10_f64(double x) {
+    const double ivln10hi = 4.34294481878168880939e-01, ivln10lo = 2.50829467116452752298e-11, log10_2hi = 3.01029995663611771306e-01,
+                 log10_2lo = 3.69423907715893078616e-13;
+    const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01, Lg4 = 2.222219843214978396e-01,
+                 Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01, Lg7 = 1.479819860511658591e-01;
+    uint32_t hx = high_word(x);
+    int k = 0;
+    if (hx < 0x00100000 || hx >> 31) {
+        if (x == 0) return -1 / (x * x);      // log(+-0) = -inf
+        if (hx >> 31) return (x - x) / 0.0;   // log(negative) = NaN
+        k -= 54; x *= 0x1p54; hx = high_word(x); // subnormal
+    } else if (hx >= 0x7ff00000) {
+        return x;
+    } else if (hx == 0x3ff00000 && low_word(x) == 0) {
+        return 0;
+    }
+    hx += 0x3ff00000 - 0x3fe6a09e; // x into [sqrt(2) / 2, sqrt(2)]
+    k += (int)(hx >> 20) - 0x3ff;
+    hx = (hx & 0x000fffff) + 0x3fe6a09e;
+    x = from_words(hx, low_word(x));
+    const double f = x - 1.0, hfsq = 0.5 * f * f, s = f / (2.0 + f), z = s * s, w = z * z;
+    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6)), t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7))), R = t2 + t1;
+    double hi = f - hfsq;
+    hi = from_words(high_word(hi), 0);
+    const double lo = f - hi - hfsq + s * (hfsq + R);
+    double val_hi = hi * ivln10hi;
+    const double dk = (double)k, y = dk * log10_2hi;
+    double val_lo = dk * log10_2lo + (lo + hi) * ivln10lo + lo * ivln10hi;
+    const double ww = y + val_hi;
+    val_lo += (y - ww) + val_hi;
+    val_hi = ww;
+    return val_lo + val_hi;
+}
+
 }} // namespace zg::hostmath

@@ -17,6 +17,8 @@ float sin_f32(float x);
 float cos_f32(float x);
 double sin_f64(double x);              // Zig @sin / @cos of an f64, |x| < 2^20 pi/2: HoughTransform.init, src/image/hough.zig:52-56
 double cos_f64(double x);
+double exp_f64(double x);              // Zig @exp of an f64: generateSsimWindow, src/image/metrics.zig:242
+double log10_f64(double x);            // std.math.log10 of an f64: psnr, src/image/metrics.zig:53
 float srgb_to_linear(float c);          // gammaToLinear, src/color.zig:1252-1258
 const float *srgb_u8_lut();             // [256], gammaToLinear(i / 255)
 const float *lanczos3_lut();            // [1025], src/image/interpolation.zig:256-267

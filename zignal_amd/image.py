@@ -290,6 +290,65 @@ class Image:
                                           C.c_void_p(count.data_ptr()) if count is not None else None, self._stream()))
         return self
 
+    # ---- metrics (reference src/image/metrics.zig) -------------------------------------------------------------------------
+    def _metric(self, name: str, other: "Image", result, window=None, ssim_map=None):
+        from . import metrics as M
+        other = self._wrap(other)
+        self._same_side(other)
+        opt = L.ZgMetricOptions(None, None)
+        if window is not None:
+            window = np.ascontiguousarray(window, np.float64)
+            if window.size != 121:
+                raise ValueError("window: 121 f64 weights")
+            opt.ssim_window = window.ctypes.data
+        a, b = self._desc(), other._desc()
+        if not self.on_device:
+            if result is not None:
+                raise ValueError("result is a device tensor: a host image takes none")
+            if ssim_map is not None:
+                if not (isinstance(ssim_map, np.ndarray) and ssim_map.dtype == np.float64 and ssim_map.flags.c_contiguous
+                        and ssim_map.shape == (self.rows - 10, self.cols - 10)):
+                    raise ValueError("map is a C-contiguous (rows - 10, cols - 10) float64 array")
+                opt.ssim_map = ssim_map.ctypes.data
+            value = C.c_double()
+            L.check(getattr(L.lib(), f"zg_{name}_host")(C.byref(a), C.byref(b), C.byref(opt), C.byref(value), None))
+            return value.value
+        if ssim_map is not None:
+            if not (_is_torch(ssim_map) and ssim_map.is_cuda and ssim_map.device == self.data.device and ssim_map.dtype == torch.float64
+                    and ssim_map.is_contiguous() and tuple(ssim_map.shape) == (self.rows - 10, self.cols - 10)):
+                raise ValueError("map is a contiguous (rows - 10, cols - 10) float64 tensor on the image's device")
+            opt.ssim_map = ssim_map.data_ptr()
+        own = result is None
+        if own:
+            result = torch.empty(4, dtype=torch.float64, device=self.data.device)
+        elif not M._is_result_tensor(result, self.data.device):
+            raise ValueError("result is a contiguous, 8-byte aligned tensor of at least 32 bytes on the image's device")
+        with torch.cuda.device(self.data.device):
+            L.check(getattr(L.lib(), f"zg_{name}")(C.byref(a), C.byref(b), C.byref(opt), C.c_void_p(result.data_ptr()), self._stream()))
+        if not own:
+            return result
+        value = float(M._record(result)["value"])
+        return M.psnr_from_mse(value, 1.0 if self.pixel in (L.PIXEL_F32, L.PIXEL_RGB_F32, L.PIXEL_RGBA_F32) else 255.0) if name == "psnr" else value
+
+    def psnr(self, other: "Image", result=None):
+        """Image.psnr (metrics.zig:10-54): 20 log10(max) - 10 log10(mse) over every component, inf for equal images; the mse's sum has the
+        bits of the reference's left-to-right f64 loop. Host images: synchronous, returns the float. Device images: returns the float
+        after one synchronisation, or with `result` (a contiguous device tensor of at least 32 bytes, a zg_metric_result whose `value` is
+        the mse: zignal_amd.metrics.METRIC_RESULT_DTYPE) fills it asynchronously on the current stream and returns it."""
+        return self._metric("psnr", other, result)
+
+    def mean_pixel_error(self, other: "Image", result=None):
+        """Image.meanPixelError (metrics.zig:114-166): the mean absolute component difference over the component maximum (255 or 1).
+        Arguments and results as psnr; the record's `value` is the method's value."""
+        return self._metric("mean_pixel_error", other, result)
+
+    def ssim(self, other: "Image", map=None, result=None, window=None):
+        """Image.ssim (metrics.zig:56-112): the mean over every 11 x 11 window of the structural similarity of the pixels' scalars
+        (getPixelScalar), bit for bit. `map`, when given, is a contiguous (rows - 10, cols - 10) float64 array (host images) or device
+        tensor that receives every window's quotient; `window` replaces the library's 121 Gaussian weights (a Zig host's own table).
+        Arguments and results otherwise as psnr. An image below 11 x 11 raises InvalidArgument (error.ImageTooSmall)."""
+        return self._metric("ssim", other, result, window, map)
+
     def copy(self, dst: Optional["Image"] = None) -> "Image":
         dst = self._like() if dst is None else self._wrap(dst)
         self._same_side(dst)
