@@ -741,4 +741,8 @@ ZG_API void zg_jpeg_free(void *p);
  * same way (_METRICS_SIGNATURES, zig/zignal_hip_metrics.zig). */
 #include "zignal_hip_metrics.h"
 
+/* The colour histogram, median cut and lookup table of src/image/quantize.zig, the dither modes of src/image/dither.zig and
+ * mapImageToPalette: a module of its own in the same way (_QUANTIZE_SIGNATURES, zig/zignal_hip_quantize.zig). */
+#include "zignal_hip_quantize.h"
+
 #endif /* ZIGNAL_HIP_H */

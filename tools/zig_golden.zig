@@ -40,7 +40,7 @@
 //!   exp / sin / cos / cbrt / pow24 / pow_third / pow_inv24   [input, output] pairs over the argument ranges the path uses
 const std = @import("std");
 const builtin = @import("builtin");
-const zignal = @import("zignal"); // the matcher, hough and flood_fill sections alone
+const zignal = @import("zignal"); // the matcher, hough, flood_fill and quantize sections alone
 
 fn bits(x: f32) u32 {
     return @bitCast(x);
@@ -443,6 +443,57 @@ fn floodSection(w: anytype, allocator: std.mem.Allocator) !void {
     try w.print("\n  ],\n", .{});
 }
 
+// ---- quantize: the reference's own medianCut and error diffusion on inputs made here ------------------------------------------------
+/// Frames with few distinct values per channel: every sort of medianCut meets long runs of equal keys, which is where the order that
+/// std.sort.heap (unstable) leaves shows in the palette. Then both diffusion modes on noise against the two-grey palette.
+fn quantizeSection(w: anytype, allocator: std.mem.Allocator) !void {
+    const Rgb = zignal.Rgb(u8);
+    const levels = [_]u8{ 0, 8, 64, 72, 200, 248 };
+    try w.print("  \"quantize\": {{\"median_cut\": [", .{});
+    var first = true;
+    for ([_]u32{ 101, 102, 103 }, [_]u32{ 48, 31, 64 }, [_]u32{ 48, 77, 64 }, [_]bool{ true, true, false }) |seed, rows, cols, few| {
+        var rng = Lcg{ .s = seed };
+        var img: zignal.Image(Rgb) = try .init(allocator, rows, cols);
+        defer img.deinit(allocator);
+        for (img.data) |*p| {
+            p.* = if (few)
+                Rgb{ .r = levels[(rng.next() >> 16) % 6], .g = levels[(rng.next() >> 16) % 6], .b = levels[(rng.next() >> 16) % 6] }
+            else
+                Rgb{ .r = @intCast(rng.next() >> 24), .g = @intCast(rng.next() >> 24), .b = @intCast(rng.next() >> 24) };
+        }
+        try w.print("{s}\n   {{\"rows\": {d}, \"cols\": {d}, \"data\": ", .{ if (first) "" else ",", rows, cols });
+        first = false;
+        try printBytes(w, std.mem.sliceAsBytes(img.data));
+        try w.print(", \"palettes\": [", .{});
+        for ([_]u16{ 2, 5, 16, 64, 256 }, 0..) |max_colors, i| {
+            var palette: [256]Rgb = undefined;
+            const n = try zignal.quantize.medianCut(Rgb, allocator, img, &palette, max_colors);
+            try w.print("{s}{{\"max_colors\": {d}, \"palette\": ", .{ if (i == 0) "" else ", ", max_colors });
+            try printBytes(w, std.mem.sliceAsBytes(palette[0..n]));
+            try w.print("}}", .{});
+        }
+        try w.print("]}}", .{});
+    }
+    try w.print("\n  ], \"dither\": [", .{});
+    const greys = [_]Rgb{ .{ .r = 64, .g = 64, .b = 64 }, .{ .r = 192, .g = 192, .b = 192 } };
+    const lut: zignal.quantize.ColorLookupTable = .init(&greys);
+    first = true;
+    for ([_]zignal.dither.Mode{ .floyd_steinberg, .atkinson, .ordered }) |mode| {
+        var rng = Lcg{ .s = 104 };
+        var img: zignal.Image(Rgb) = try .init(allocator, 37, 53);
+        defer img.deinit(allocator);
+        for (img.data) |*p| p.* = .{ .r = @intCast(rng.next() >> 24), .g = @intCast(rng.next() >> 24), .b = @intCast(rng.next() >> 24) };
+        try w.print("{s}\n   {{\"mode\": {d}, \"rows\": 37, \"cols\": 53, \"data\": ", .{ if (first) "" else ",", @intFromEnum(mode) });
+        first = false;
+        try printBytes(w, std.mem.sliceAsBytes(img.data));
+        zignal.dither.apply(img, &greys, lut, mode);
+        try w.print(", \"out\": ", .{});
+        try printBytes(w, std.mem.sliceAsBytes(img.data));
+        try w.print("}}", .{});
+    }
+    try w.print("\n  ]}},\n", .{});
+}
+
 // ---- metrics: the host arithmetic of psnr and ssim in f64 -----------------------------------------------------------------------------
 fn runtime64(x: f64) f64 {
     var v = x;
@@ -603,6 +654,9 @@ pub fn main(init: std.process.Init) !void {
 
     // src/image/metrics.zig:53, 230-249
     try metricsSection(w);
+
+    // src/image/quantize.zig:175-412 and src/image/dither.zig:34-331 through the zignal module
+    try quantizeSection(w, init.gpa);
 
     // src/features/orb.zig:340-357 (the table), :424-425 (radiansToDegrees(atan2(m01 / m00, m10 / m00)): centroid offsets lie within the
     // 15-pixel patch), :432-433 (@cos / @sin of degreesToRadians(angle), angle in [-180, 180])

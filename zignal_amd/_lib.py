@@ -412,6 +412,26 @@ _METRICS_SIGNATURES = {
 _METRICS_RESTYPES = {"zg_sum_f64_chunk": C.c_uint32, "zg_psnr_from_mse": C.c_double, "zg_exp_f64_host": C.c_double, "zg_log10_f64_host": C.c_double}
 METRICS_EXPORTED_SYMBOLS = tuple(_METRICS_SIGNATURES)
 
+# the quantisation module: every symbol include/zignal_hip_quantize.h declares
+_U8P = C.POINTER(C.c_uint8)
+_QUANTIZE_SIGNATURES = {
+    "zg_color_histogram": [_IMG, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_median_cut_from_histogram_host": [_U32P, _U32P, C.c_uint32, C.c_uint32, _U8P, _U32P],
+    "zg_median_cut": [_IMG, C.c_uint32, C.c_uint32, _U8P, _U32P],
+    "zg_build_palette": [_IMG, C.c_int, C.c_uint32, _U8P, _U32P],
+    "zg_palette_lut": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_palette_lut_host": [_U8P, C.c_uint32, _U8P],
+    "zg_dither_geometry": [_U32P, _U32P, _U32P],
+    "zg_dither": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p],
+    "zg_dither_frames": [_IMG, C.c_uint32, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p],
+    "zg_palette_map": [_IMG, _IMG, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p],
+}
+_QUANTIZE_RESTYPES = {"zg_dither_geometry": None}
+QUANTIZE_EXPORTED_SYMBOLS = tuple(_QUANTIZE_SIGNATURES)
+HISTOGRAM_CELLS, HISTOGRAM_UNTOUCHED = 32768, 0xFFFFFFFF  # ZG_HISTOGRAM_CELLS, ZG_HISTOGRAM_UNTOUCHED
+DITHER_NONE, DITHER_FLOYD_STEINBERG, DITHER_ATKINSON, DITHER_ORDERED, DITHER_AUTO = range(5)
+PALETTE_FIXED_6X7X6, PALETTE_FIXED_VGA16, PALETTE_FIXED_WEB216, PALETTE_ADAPTIVE = range(4)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -422,7 +442,8 @@ def lib() -> C.CDLL:
                 "(hipcc --offload-arch=gfx950). zignal_amd has no CPU fallback.")
         l = C.CDLL(LIB_PATH)
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
-                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES)):
+                                (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
+                                (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

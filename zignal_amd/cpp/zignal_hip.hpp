@@ -84,6 +84,33 @@ struct FloodFillOptions {                                                       
     ThresholdMode mode = ThresholdMode::seed;
     zg_flood_fill_options c_options() const { return zg_flood_fill_options{threshold, (int)connectivity, (int)mode}; }
 };
+// dither.Mode (dither.zig:18-30) and PaletteMode (quantize.zig:476-498) with the reference's ordinals, and a palette of up to 256 colours
+enum class DitherMode : int { none = ZG_DITHER_NONE, floyd_steinberg = ZG_DITHER_FLOYD_STEINBERG, atkinson = ZG_DITHER_ATKINSON, ordered = ZG_DITHER_ORDERED,
+                              automatic = ZG_DITHER_AUTO };
+struct PaletteMode {
+    int kind;
+    uint32_t max_colors = 256;
+    static PaletteMode fixed6x7x6() { return {ZG_PALETTE_FIXED_6X7X6}; }
+    static PaletteMode fixedVga16() { return {ZG_PALETTE_FIXED_VGA16}; }
+    static PaletteMode fixedWeb216() { return {ZG_PALETTE_FIXED_WEB216}; }
+    static PaletteMode adaptive(uint32_t max_colors = 256) { return {ZG_PALETTE_ADAPTIVE, max_colors}; }
+};
+struct Palette {
+    Rgb<uint8_t> colors[256];
+    uint32_t size = 0;
+    // the fixed palettes of buildPalette (quantize.zig:502-521): host tables, no GPU needed
+    static Palette fixed(PaletteMode mode) {
+        Palette p;
+        check(zg_build_palette(nullptr, mode.kind, mode.max_colors, &p.colors[0].r, &p.size));
+        return p;
+    }
+    // ColorLookupTable.init (quantize.zig:66-159) on the host: 32768 bytes indexed by r5 << 10 | g5 << 5 | b5
+    std::vector<uint8_t> lookupTable() const {
+        std::vector<uint8_t> lut(ZG_HISTOGRAM_CELLS);
+        check(zg_palette_lut_host(&colors[0].r, size, lut.data()));
+        return lut;
+    }
+};
 template <typename T> struct Rectangle { T l, t, r, b; T width() const { return l >= r ? T(0) : r - l; } T height() const { return t >= b ? T(0) : b - t; } };
 struct ProjectiveTransform { float m[9]; };                                              // geometry/transforms.zig:197
 
@@ -280,6 +307,40 @@ template <template <typename> class Img, typename T> class Ops {
         if constexpr (Derived::on_device) check(zg_flood_fill(&s, row, col, seed_device, (const void *)&fill_value, &o, filled_count_device, self().stream()));
         else check(zg_flood_fill_host(&s, row, col, (const void *)&fill_value, &o, &filled));
         return filled;
+    }
+    // ---- quantisation and dithering (quantize.zig, dither.zig, gif.zig:875-920): DeviceImage only, enqueued on stream() ----
+    // counts_device and first_device are 32768 device words each (quantize.zig:188-237; first: the raster index of a cell's first pixel)
+    void colorHistogram(uint32_t *counts_device, uint32_t *first_device) const {
+        static_assert(Derived::on_device, "colorHistogram is a device operation");
+        const zg_image s = desc();
+        check(zg_color_histogram(&s, counts_device, first_device, self().stream()));
+    }
+    // medianCut (quantize.zig:175-412) into a host palette; synchronises the default stream once
+    Palette medianCut(uint32_t max_colors = 256) const {
+        static_assert(Derived::on_device, "medianCut is a device operation");
+        Palette p;
+        const zg_image s = desc();
+        check(zg_median_cut(&s, max_colors, 256, &p.colors[0].r, &p.size));
+        return p;
+    }
+    Palette buildPalette(PaletteMode mode) const {                                       // quantize.zig:502-527
+        static_assert(Derived::on_device, "buildPalette is a device operation");
+        Palette p;
+        const zg_image s = desc();
+        check(zg_build_palette(&s, mode.kind, mode.max_colors, &p.colors[0].r, &p.size));
+        return p;
+    }
+    // dither.apply (dither.zig:34-41), in place on an Rgb(u8) image; the palette and its table (zg_palette_lut) are device memory
+    void dither(const Rgb<uint8_t> *palette_device, uint32_t n, const uint8_t *lut_device, DitherMode mode) const {
+        static_assert(Derived::on_device, "dither is a device operation");
+        const zg_image s = desc();
+        check(zg_dither(&s, &palette_device->r, n, lut_device, (int)mode, self().stream()));
+    }
+    // mapImageToPalette (gif.zig:875-920) into a u8 index plane of the same shape; transparent_index < 0: none
+    void mapToPalette(const Of<uint8_t> &indices, const Rgb<uint8_t> *palette_device, uint32_t n, bool use_dither, int transparent_index = -1) const {
+        static_assert(Derived::on_device, "mapToPalette is a device operation");
+        const zg_image s = desc(), d = indices.desc();
+        check(zg_palette_map(&s, &d, &palette_device->r, n, use_dither ? 1 : 0, transparent_index, self().stream()));
     }
     // ---- metrics (metrics.zig:10-54 psnr, :56-112 ssim, :114-166 meanPixelError) ----
     // An Image is measured synchronously and the method's f64 returned. A DeviceImage's metric is enqueued on stream(): with

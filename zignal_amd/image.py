@@ -349,6 +349,32 @@ class Image:
         Arguments and results otherwise as psnr. An image below 11 x 11 raises InvalidArgument (error.ImageTooSmall)."""
         return self._metric("ssim", other, result, window, map)
 
+    # ---- quantisation and dithering (reference src/image/quantize.zig, src/image/dither.zig; zignal_amd/quantize.py) -----------------
+    def color_histogram(self, counts=None, first=None):
+        """The 32768-cell colour histogram medianCut starts from (quantize.zig:188-237) of a u8, Rgb(u8) or Rgba(u8) device image:
+        (counts, first), two device tensors of 32768 32-bit words; `first` is the raster index row * cols + col of each cell's first
+        pixel, 0xFFFFFFFF for an empty cell. Asynchronous on the current stream."""
+        from . import quantize as Q
+        return Q.color_histogram(self, counts, first)
+
+    def median_cut(self, max_colors: int = 256, capacity: int = 256) -> np.ndarray:
+        """medianCut (quantize.zig:175-412) of a device image: an (n, 3) uint8 host palette. Synchronises once."""
+        from . import quantize as Q
+        return Q.median_cut(self, max_colors, capacity)
+
+    def dither(self, palette, lut=None, mode: int = 1) -> "Image":
+        """dither.apply (dither.zig:34-41), in place on an Rgb(u8) device image: every pixel becomes a colour of `palette` (an (n, 3)
+        uint8 host array or a device tensor of 3 n bytes). `mode` is a zignal_amd.DitherMode (Floyd-Steinberg by default); `lut` is the
+        palette's device lookup table (zignal_amd.palette_lut), built here when None. Asynchronous on the current stream."""
+        from . import quantize as Q
+        return Q.dither(self, palette, lut, mode)
+
+    def map_to_palette(self, palette, use_dither: bool = False, transparent_index=None, out: Optional["Image"] = None) -> "Image":
+        """mapImageToPalette (gif.zig:875-920): the u8 index plane of a u8, Rgb(u8) or Rgba(u8) device image, with Floyd-Steinberg when
+        `use_dither`. `transparent_index` reserves the palette's last entry and is given to Rgba pixels whose alpha is below 128."""
+        from . import quantize as Q
+        return Q.map_to_palette(self, palette, use_dither, transparent_index, out)
+
     def copy(self, dst: Optional["Image"] = None) -> "Image":
         dst = self._like() if dst is None else self._wrap(dst)
         self._same_side(dst)
