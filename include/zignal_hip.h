@@ -381,8 +381,10 @@ ZG_API int zg_invert_host(const zg_image *img);
 /* Image(T).medianBlur / percentileBlur / minBlur / maxBlur / midpointBlur / alphaTrimmedMeanBlur (src/image.zig:653-783
  * -> src/image/order_statistic_blur.zig) for u8 and all-u8 struct pixels, per channel. op 0: percentile (param in
  * [0, 1]; median = 0.5 with ZG_BORDER_MIRROR, min = 0.0, max = 1.0), 1: midpoint, 2: alpha-trimmed mean (param = trim
- * fraction in [0, 0.5)). InvalidPercentile / InvalidTrim -> ZG_ERR_INVALID_ARGUMENT, UnsupportedPixelType and radius > 15
- * -> ZG_ERR_UNSUPPORTED. radius 0 copies. src may alias dst. */
+ * fraction in [0, 0.5)). InvalidPercentile / InvalidTrim -> ZG_ERR_INVALID_ARGUMENT, UnsupportedPixelType and radius > 256
+ * (the bound of the reference CLI's `blur median`) -> ZG_ERR_UNSUPPORTED. radius 0 copies. src may alias dst. Two kernels:
+ * k_order_stat evaluates every window directly (radius 1..15), k_order_stat_hist slides a 256-bin histogram per output
+ * column down the frame, work linear in the radius (radius 16..256). */
 ZG_API int zg_order_statistic_blur(const zg_image *src, const zg_image *dst, uint32_t radius, int op, double param, int border,
                                    zg_stream stream);
 ZG_API int zg_order_statistic_blur_host(const zg_image *src, const zg_image *dst, uint32_t radius, int op, double param, int border);

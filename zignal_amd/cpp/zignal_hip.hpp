@@ -147,6 +147,12 @@ template <template <typename> class Img, typename T> class Ops {
         if constexpr (Derived::on_device) check(dev(a..., self().stream()));
         else check(host(a...));
     }
+    // op: 0 percentile, 1 midpoint, 2 alpha-trimmed mean (zg_order_statistic_blur)
+    void orderStatistic(const Derived &out, uint32_t radius, int op, double param, BorderMode border, const char *what) const {
+        if (!hasSameShape(out)) throw DimensionMismatch(1, what);
+        const zg_image s = desc(), d = out.desc();
+        run(zg_order_statistic_blur, zg_order_statistic_blur_host, &s, &d, radius, op, param, (int)border);
+    }
     // psnr, meanPixelError and ssim: see the public methods
     template <class DevFn, class HostFn>
     double metric(DevFn dev, HostFn host, const Derived &other, const zg_metric_options &opt, zg_metric_result *result_device, bool is_psnr) const {
@@ -207,6 +213,22 @@ template <template <typename> class Img, typename T> class Ops {
         if (!hasSameShape(out)) throw DimensionMismatch(1, "medianBlur");
         const zg_image s = desc(), d = out.desc();
         run(zg_order_statistic_blur, zg_order_statistic_blur_host, &s, &d, radius, 0, 0.5, (int)ZG_BORDER_MIRROR);
+    }
+    // the other order-statistic blurs (image.zig:672-783): radius up to 256, u8 and all-u8 struct pixels
+    void percentileBlur(const Derived &out, uint32_t radius, double percentile, BorderMode border) const {     // image.zig:672
+        orderStatistic(out, radius, 0, percentile, border, "percentileBlur");
+    }
+    void minBlur(const Derived &out, uint32_t radius, BorderMode border) const {                               // image.zig:696
+        orderStatistic(out, radius, 0, 0.0, border, "minBlur");
+    }
+    void maxBlur(const Derived &out, uint32_t radius, BorderMode border) const {                               // image.zig:719
+        orderStatistic(out, radius, 0, 1.0, border, "maxBlur");
+    }
+    void midpointBlur(const Derived &out, uint32_t radius, BorderMode border) const {                          // image.zig:742
+        orderStatistic(out, radius, 1, 0.0, border, "midpointBlur");
+    }
+    void alphaTrimmedMeanBlur(const Derived &out, uint32_t radius, double trim_fraction, BorderMode border) const { // image.zig:767
+        orderStatistic(out, radius, 2, trim_fraction, border, "alphaTrimmedMeanBlur");
     }
     void equalize() const { const zg_image s = desc(); run(zg_equalize, zg_equalize_host, &s); } // image.zig:824 (in place)
     void sharpen(const Derived &out, uint32_t radius) const {                             // image.zig:785

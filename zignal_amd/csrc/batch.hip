@@ -46,7 +46,7 @@ int apply_shape(const zg_step &st, Frames &f) { // what a step does to shape and
         ZG_REQUIRE(st.sigma >= 0, ZG_ERR_INVALID_ARGUMENT, "pipeline: InvalidSigma (%g)", st.sigma);
         return ZG_OK;
     case ZG_STEP_BOX_BLUR: return ZG_OK;
-    case ZG_STEP_MEDIAN_BLUR: // the CLI's own limit (src/cli/blur.zig:118-121); the kernel's is lower and reported when the step runs
+    case ZG_STEP_MEDIAN_BLUR: // the CLI's own limit (src/cli/blur.zig:118-121), which is also the kernels': radius <= 256 (order_stat.hip: k_order_stat to 15, k_order_stat_hist from 16)
         ZG_REQUIRE(st.radius <= 256, ZG_ERR_INVALID_ARGUMENT, "pipeline: median blur radius %u exceeds 256", st.radius);
         return ZG_OK;
     case ZG_STEP_MOTION_BLUR:
