@@ -747,4 +747,8 @@ ZG_API void zg_jpeg_free(void *p);
  * mapImageToPalette: a module of its own in the same way (_QUANTIZE_SIGNATURES, zig/zignal_hip_quantize.zig). */
 #include "zignal_hip_quantize.h"
 
+/* Canvas(T)'s lines, rectangles, circles and polygons (src/canvas/Canvas.zig) as one device operation over a command list: a module of
+ * its own in the same way (_CANVAS_SIGNATURES, zig/zignal_hip_canvas.zig). */
+#include "zignal_hip_canvas.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -135,6 +135,17 @@ class ZgFloodFillOptions(C.Structure):
 FLOOD_MODE_SEED, FLOOD_MODE_NEIGHBOR = range(2)
 
 
+class ZgDrawCmd(C.Structure):
+    """zg_draw_cmd: one call of the reference's Canvas(T) (include/zignal_hip_canvas.h). 40 bytes."""
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("width", C.c_uint32), ("color", C.c_uint8 * 4), ("p", C.c_float * 4),
+                ("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32)]
+
+
+DRAW_LINE, DRAW_RECT, DRAW_FILL_RECT, DRAW_CIRCLE, DRAW_FILL_CIRCLE, DRAW_POLYGON, DRAW_FILL_POLYGON = range(7)
+DRAW_FAST, DRAW_SOFT = range(2)
+CANVAS_MAX_VERTICES, CANVAS_MAX_COORD, CANVAS_MAX_WIDTH, CANVAS_MAX_SIZE, CANVAS_MAX_COMMANDS = 64, 65536.0, 65536, 32768, 1 << 24  # ZG_CANVAS_MAX_*
+
+
 class ZgMetricResult(C.Structure):
     """zg_metric_result: the left-to-right f64 sum, the number of terms, the metric's value and how many terms were added serially."""
     _fields_ = [("sum", C.c_double), ("count", C.c_uint64), ("value", C.c_double), ("serial_terms", C.c_uint64)]
@@ -432,6 +443,18 @@ HISTOGRAM_CELLS, HISTOGRAM_UNTOUCHED = 32768, 0xFFFFFFFF  # ZG_HISTOGRAM_CELLS, 
 DITHER_NONE, DITHER_FLOYD_STEINBERG, DITHER_ATKINSON, DITHER_ORDERED, DITHER_AUTO = range(5)
 PALETTE_FIXED_6X7X6, PALETTE_FIXED_VGA16, PALETTE_FIXED_WEB216, PALETTE_ADAPTIVE = range(4)
 
+# the Canvas module: every symbol include/zignal_hip_canvas.h declares
+_CANVAS_SIGNATURES = {
+    "zg_sizeof_draw_cmd": [],
+    "zg_canvas_tile": [],
+    "zg_canvas_draw": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "zg_canvas_draw_host": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32],
+    "zg_canvas_cmds_from_hough_lines": [C.c_void_p, C.c_void_p, C.c_uint32, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_canvas_cmds_from_keypoints": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+_CANVAS_RESTYPES = {"zg_sizeof_draw_cmd": C.c_size_t, "zg_canvas_tile": C.c_uint32}
+CANVAS_EXPORTED_SYMBOLS = tuple(_CANVAS_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -443,13 +466,15 @@ def lib() -> C.CDLL:
         l = C.CDLL(LIB_PATH)
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
-                                (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES)):
+                                (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes
                 fn.restype = restypes.get(name, C.c_int)
         if l.zg_sizeof_step() != C.sizeof(ZgStep):  # zg_step has no size field: a library built from another header must not be handed ZgStep arrays
             raise ImportError(f"{LIB_PATH}: sizeof(zg_step) is {l.zg_sizeof_step()} in the library, {C.sizeof(ZgStep)} in this binding: rebuild the library")
+        if l.zg_sizeof_draw_cmd() != C.sizeof(ZgDrawCmd):  # the same rule for zg_draw_cmd arrays
+            raise ImportError(f"{LIB_PATH}: sizeof(zg_draw_cmd) is {l.zg_sizeof_draw_cmd()} in the library, {C.sizeof(ZgDrawCmd)} in this binding: rebuild the library")
         _lib = l
     return _lib
 

@@ -1,0 +1,198 @@
+"""Canvas(T) (reference src/canvas/Canvas.zig) over the zg_canvas_* entry points (include/zignal_hip_canvas.h): lines, rectangles,
+circles and polygons drawn into a u8, Rgb(u8) or Rgba(u8) image in place, as one device operation over a command list. The result
+equals the reference making the same calls one after another, byte for byte.
+
+    cv = zg.Canvas(image)                       # a device (or host) zg.Image or the tensor / array under it
+    cv.draw_line((10, 20), (90, 70), (255, 0, 0, 255), width=2, mode="soft")
+    cv.fill_circle((50, 50), 12.5, (0, 255, 0, 128), mode="soft")
+    cv.flush()                                  # uploads the list and draws it: asynchronous on the current stream
+
+Colours are Rgba(u8) tuples (three values mean a = 255)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .image import Image, KEYPOINT_DTYPE, _is_torch, torch
+from .hough import HOUGH_LINE_DTYPE
+
+# zg_draw_cmd as a numpy structured dtype: the bytes of the C struct
+DRAW_CMD_DTYPE = np.dtype([("kind", "<i4"), ("mode", "<i4"), ("width", "<u4"), ("color", "u1", (4,)), ("p", "<f4", (4,)),
+                           ("first_vertex", "<u4"), ("n_vertices", "<u4")])
+assert DRAW_CMD_DTYPE.itemsize == C.sizeof(L.ZgDrawCmd)
+_MODES = {"fast": L.DRAW_FAST, "soft": L.DRAW_SOFT}
+
+
+def _mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in _MODES:
+            raise L.InvalidArgument(L.ERR_INVALID_ARGUMENT, f"canvas: mode {mode!r} (\"fast\" or \"soft\")")
+        return _MODES[mode]
+    return int(mode)
+
+
+def _color(color):
+    c = tuple(int(v) for v in color)
+    if len(c) == 3:
+        c += (255,)
+    if len(c) != 4 or any(v < 0 or v > 255 for v in c):
+        raise L.InvalidArgument(L.ERR_INVALID_ARGUMENT, f"canvas: colour {color!r} (r, g, b[, a] in 0..255)")
+    return c
+
+
+def canvas_tile() -> int:
+    """The side of the pixel tiles a workgroup rasterises (zg_canvas_tile)."""
+    return int(L.lib().zg_canvas_tile())
+
+
+def pack_commands(commands):
+    """A list of command dicts — kind (zignal_amd._lib.DRAW_*), mode, width, color and p (the float parameters) or pts (polygon
+    vertices) — as (a DRAW_CMD_DTYPE array, an (n_vertices, 2) float32 array): the host form of zg_canvas_draw's two lists."""
+    cmds = np.zeros(len(commands), DRAW_CMD_DTYPE)
+    vertices = []
+    for i, c in enumerate(commands):
+        cmds[i]["kind"], cmds[i]["mode"], cmds[i]["width"] = int(c["kind"]), _mode(c.get("mode", L.DRAW_FAST)), int(c.get("width", 1))
+        cmds[i]["color"] = _color(c["color"])
+        if "pts" in c:
+            cmds[i]["first_vertex"], cmds[i]["n_vertices"] = len(vertices), len(c["pts"])
+            vertices += [(float(x), float(y)) for x, y in c["pts"]]
+        else:
+            p = [float(v) for v in c["p"]]
+            cmds[i]["p"] = p + [0.0] * (4 - len(p))
+    return cmds, np.asarray(vertices, np.float32).reshape(-1, 2)
+
+
+def draw_host(image, cmds: np.ndarray, vertices=None) -> None:
+    """zg_canvas_draw_host: host pixels (a numpy array or a host zg.Image), a DRAW_CMD_DTYPE array and float32 vertex pairs. Synchronous;
+    a command outside the contract raises InvalidArgument (a polygon of more than 64 vertices: ZignalError, unsupported)."""
+    img = image if isinstance(image, Image) else Image(image)
+    cmds = np.ascontiguousarray(cmds, DRAW_CMD_DTYPE)
+    v = np.ascontiguousarray(np.zeros((0, 2), np.float32) if vertices is None else vertices, np.float32).reshape(-1, 2)
+    d = img._desc()
+    L.check(L.lib().zg_canvas_draw_host(C.byref(d), cmds.ctypes.data if len(cmds) else None, len(cmds), v.ctypes.data if len(v) else None, len(v)))
+
+
+def _bytes_of(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def draw(image, cmds, count=None, vertices=None, n=None) -> None:
+    """zg_canvas_draw, the device-list form: `cmds` is a device tensor holding zg_draw_cmd structs (n of them; by default as many as it
+    holds), `count` an optional device tensor whose first 4 bytes are the number of commands to execute (at most n), `vertices` a
+    float32 device tensor of (x, y) pairs. Asynchronous on the current stream; nothing is synchronised, copied or uploaded."""
+    img = image if isinstance(image, Image) else Image(image)
+    if not img.on_device or not _is_torch(cmds) or (count is not None and not _is_torch(count)) or (vertices is not None and not _is_torch(vertices)):
+        raise ValueError("draw takes a device image and device tensors")
+    cap = _bytes_of(cmds) // DRAW_CMD_DTYPE.itemsize
+    n = cap if n is None else int(n)
+    if n > cap or (count is not None and _bytes_of(count) < 4):
+        raise ValueError("cmds or count tensor too small")
+    if vertices is not None and (vertices.dtype != torch.float32 or not vertices.is_contiguous()):
+        raise ValueError("vertices must be a contiguous float32 tensor of (x, y) pairs")
+    nv = 0 if vertices is None else vertices.numel() // 2
+    d = img._desc()
+    with torch.cuda.device(img.data.device):
+        L.check(L.lib().zg_canvas_draw(C.byref(d), C.c_void_p(cmds.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
+                                       C.c_void_p(vertices.data_ptr()) if nv else None, nv, img._stream()))
+
+
+def _builder_out(list_tensor, itemsize, cmds_out, count_out):
+    cap = _bytes_of(list_tensor) // itemsize
+    dev = list_tensor.device
+    if cmds_out is None:
+        cmds_out = torch.zeros(max(cap, 1) * DRAW_CMD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    if count_out is None:
+        count_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    cap = min(cap, _bytes_of(cmds_out) // DRAW_CMD_DTYPE.itemsize)
+    return cap, cmds_out, count_out
+
+
+def cmds_from_hough_lines(lines, counts, color, width: int = 1, mode="fast", cmds_out=None, count_out=None):
+    """zg_canvas_cmds_from_hough_lines: one line command from p1 to p2 per line of HoughTransform.find_lines_into's device list (`lines`,
+    `counts`: its two count words). Returns (cmds, count) device tensors for draw(); asynchronous on the current stream."""
+    cap, cmds_out, count_out = _builder_out(lines, HOUGH_LINE_DTYPE.itemsize, cmds_out, count_out)
+    col = (C.c_uint8 * 4)(*_color(color))
+    with torch.cuda.device(lines.device):
+        stream = C.c_void_p(torch.cuda.current_stream(lines.device).cuda_stream)
+        L.check(L.lib().zg_canvas_cmds_from_hough_lines(C.c_void_p(lines.data_ptr()), C.c_void_p(counts.data_ptr()), cap, col, int(width), _mode(mode),
+                                                        C.c_void_p(cmds_out.data_ptr()), C.c_void_p(count_out.data_ptr()), stream))
+    return cmds_out, count_out
+
+
+def cmds_from_keypoints(keypoints, count, radius: float, color, width: int = 1, mode="fast", cmds_out=None, count_out=None):
+    """zg_canvas_cmds_from_keypoints: one circle outline of `radius` at each keypoint's (x, y) of a detector's device list (`keypoints`,
+    `count`: its count word). Returns (cmds, count) device tensors for draw(); asynchronous on the current stream."""
+    cap, cmds_out, count_out = _builder_out(keypoints, KEYPOINT_DTYPE.itemsize, cmds_out, count_out)
+    col = (C.c_uint8 * 4)(*_color(color))
+    with torch.cuda.device(keypoints.device):
+        stream = C.c_void_p(torch.cuda.current_stream(keypoints.device).cuda_stream)
+        L.check(L.lib().zg_canvas_cmds_from_keypoints(C.c_void_p(keypoints.data_ptr()), C.c_void_p(count.data_ptr()), cap, float(radius), col, int(width),
+                                                      _mode(mode), C.c_void_p(cmds_out.data_ptr()), C.c_void_p(count_out.data_ptr()), stream))
+    return cmds_out, count_out
+
+
+class Canvas:
+    """Canvas(T): the draw methods append to a command list, flush() executes it into the image in list order and empties it."""
+
+    def __init__(self, image):
+        self.image = image if isinstance(image, Image) else Image(image)
+        self.commands = []
+
+    def _add(self, kind, color, width, mode, p=None, pts=None):
+        c = {"kind": kind, "mode": _mode(mode), "width": int(width), "color": _color(color)}
+        if pts is not None:
+            c["pts"] = [(float(x), float(y)) for x, y in pts]
+        else:
+            c["p"] = [float(v) for v in p]
+        self.commands.append(c)
+        return self
+
+    def draw_line(self, p1, p2, color, width: int = 1, mode="fast"):
+        return self._add(L.DRAW_LINE, color, width, mode, (p1[0], p1[1], p2[0], p2[1]))
+
+    def draw_rectangle(self, rect, color, width: int = 1, mode="fast"):
+        """rect = (l, t, r, b), r and b exclusive."""
+        return self._add(L.DRAW_RECT, color, width, mode, rect)
+
+    def fill_rectangle(self, rect, color, mode="fast"):
+        return self._add(L.DRAW_FILL_RECT, color, 1, mode, rect)
+
+    def draw_circle(self, center, radius: float, color, width: int = 1, mode="fast"):
+        return self._add(L.DRAW_CIRCLE, color, width, mode, (center[0], center[1], radius))
+
+    def fill_circle(self, center, radius: float, color, mode="fast"):
+        return self._add(L.DRAW_FILL_CIRCLE, color, 1, mode, (center[0], center[1], radius))
+
+    def draw_polygon(self, points, color, width: int = 1, mode="fast"):
+        return self._add(L.DRAW_POLYGON, color, width, mode, pts=points)
+
+    def fill_polygon(self, points, color, mode="fast"):
+        return self._add(L.DRAW_FILL_POLYGON, color, 1, mode, pts=points)
+
+    def flush(self, stream=None) -> None:
+        """Draw the list and empty it. Device image: the two lists are uploaded (one synchronous copy each) and zg_canvas_draw runs on
+        `stream` (a torch stream; default: the current one). Host image: zg_canvas_draw_host."""
+        commands, self.commands = self.commands, []
+        if not commands:
+            return
+        cmds, vertices = pack_commands(commands)
+        if not self.image.on_device:
+            draw_host(self.image, cmds, vertices)
+            return
+        dev = self.image.data.device
+        dcmds = torch.from_numpy(cmds.view(np.uint8)).to(dev)
+        dverts = torch.from_numpy(vertices).to(dev) if len(vertices) else None
+        if stream is None:
+            draw(self.image, dcmds, vertices=dverts)
+        else:
+            with torch.cuda.stream(stream):
+                draw(self.image, dcmds, vertices=dverts)
+            dcmds.record_stream(stream)
+            if dverts is not None:
+                dverts.record_stream(stream)
+
+    def draw(self, cmds_tensor, count=None, vertices=None) -> None:
+        """The device-list form: see zignal_amd.canvas.draw."""
+        draw(self.image, cmds_tensor, count, vertices)

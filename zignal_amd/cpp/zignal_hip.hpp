@@ -964,4 +964,87 @@ inline void HoughTransform::computeInto(const DeviceImage<uint8_t> &edges, const
     check(zg_hough_compute(h_, &e, box.l, box.t, box.r, box.b, accumulator, acc_stride, stream));
 }
 
+// ---- canvas: Canvas(T) (src/canvas/Canvas.zig) ----
+enum class DrawMode { fast = ZG_DRAW_FAST, soft = ZG_DRAW_SOFT };                         // Canvas.zig:19-24
+struct Point2 { float x, y; };
+// Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods append to a command list, flush()
+// executes it into the image in list order (zg_canvas_draw_host for host pixels; for device pixels the two lists are uploaded and
+// zg_canvas_draw runs on the image's stream) and empties it. The result equals the reference making the same calls, byte for byte.
+template <typename T, template <class> class Img = Image> class Canvas {
+  public:
+    static_assert(PixelTraits<T>::pixel == ZG_PIXEL_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGB_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGBA_U8,
+                  "Canvas draws on u8, Rgb<uint8_t> and Rgba<uint8_t> images");
+    explicit Canvas(const Img<T> &image) : image_(&image) {
+        if (zg_sizeof_draw_cmd() != sizeof(zg_draw_cmd)) // the zg_sizeof_step rule
+            throw Error(ZG_ERR_INVALID_ARGUMENT, "libzignal_hip: sizeof(zg_draw_cmd) is " + std::to_string(zg_sizeof_draw_cmd()) + " in the library, " +
+                                                     std::to_string(sizeof(zg_draw_cmd)) + " in this header");
+    }
+    Canvas &drawLine(Point2 p1, Point2 p2, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return add(ZG_DRAW_LINE, mode, width, color, p1.x, p1.y, p2.x, p2.y);
+    }
+    Canvas &drawRectangle(Rectangle<float> r, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return add(ZG_DRAW_RECT, mode, width, color, r.l, r.t, r.r, r.b);
+    }
+    Canvas &fillRectangle(Rectangle<float> r, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) { return add(ZG_DRAW_FILL_RECT, mode, 1, color, r.l, r.t, r.r, r.b); }
+    Canvas &drawCircle(Point2 center, float radius, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return add(ZG_DRAW_CIRCLE, mode, width, color, center.x, center.y, radius, 0.0f);
+    }
+    Canvas &fillCircle(Point2 center, float radius, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) {
+        return add(ZG_DRAW_FILL_CIRCLE, mode, 1, color, center.x, center.y, radius, 0.0f);
+    }
+    Canvas &drawPolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_POLYGON, polygon, mode, width, color);
+    }
+    Canvas &fillPolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_FILL_POLYGON, polygon, mode, 1, color);
+    }
+    const std::vector<zg_draw_cmd> &commands() const { return cmds_; }
+    void flush() {
+        std::vector<zg_draw_cmd> cmds;
+        std::vector<float> vertices;
+        cmds.swap(cmds_);
+        vertices.swap(vertices_);
+        if (cmds.empty()) return;
+        const zg_image d = image_->desc();
+        const uint32_t n = (uint32_t)cmds.size(), nv = (uint32_t)(vertices.size() / 2);
+        if constexpr (!Img<T>::on_device) {
+            check(zg_canvas_draw_host(&d, cmds.data(), n, nv ? vertices.data() : nullptr, nv));
+        } else {
+            void *mem = nullptr;
+            const size_t cmd_bytes = (cmds.size() * sizeof(zg_draw_cmd) + 255) / 256 * 256;
+            check(zg_malloc(&mem, cmd_bytes + vertices.size() * sizeof(float) + 256));
+            int rc = zg_memcpy_h2d(mem, cmds.data(), cmds.size() * sizeof(zg_draw_cmd), image_->stream());
+            if (!rc && nv) rc = zg_memcpy_h2d((char *)mem + cmd_bytes, vertices.data(), vertices.size() * sizeof(float), image_->stream());
+            if (!rc) rc = zg_canvas_draw(&d, (const zg_draw_cmd *)mem, n, nullptr, nv ? (const float *)((char *)mem + cmd_bytes) : nullptr, nv, image_->stream());
+            (void)zg_free(mem); // waits for the draw that reads the lists
+            check(rc);
+        }
+    }
+    // the device-list form: every pointer is device memory; asynchronous, nothing is synchronised, recordable into a graph
+    void draw(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device = nullptr, const float *vertices = nullptr, uint32_t n_vertices = 0) const {
+        const zg_image d = image_->desc();
+        check(zg_canvas_draw(&d, cmds, n, count_device, vertices, n_vertices, image_->stream()));
+    }
+
+  private:
+    Canvas &add(int kind, DrawMode mode, uint32_t width, Rgba<uint8_t> color, float a, float b, float c, float e) {
+        zg_draw_cmd cmd{};
+        cmd.kind = kind; cmd.mode = (int32_t)mode; cmd.width = width;
+        cmd.color[0] = color.r; cmd.color[1] = color.g; cmd.color[2] = color.b; cmd.color[3] = color.a;
+        cmd.p[0] = a; cmd.p[1] = b; cmd.p[2] = c; cmd.p[3] = e;
+        cmds_.push_back(cmd);
+        return *this;
+    }
+    Canvas &addPolygon(int kind, const std::vector<Point2> &polygon, DrawMode mode, uint32_t width, Rgba<uint8_t> color) {
+        add(kind, mode, width, color, 0, 0, 0, 0);
+        cmds_.back().first_vertex = (uint32_t)(vertices_.size() / 2);
+        cmds_.back().n_vertices = (uint32_t)polygon.size();
+        for (const Point2 &p : polygon) { vertices_.push_back(p.x); vertices_.push_back(p.y); }
+        return *this;
+    }
+    const Img<T> *image_;
+    std::vector<zg_draw_cmd> cmds_;
+    std::vector<float> vertices_;
+};
+
 } // namespace zignal

@@ -1,0 +1,722 @@
+// canvas.hip — Canvas(T) (reference src/canvas/Canvas.zig) as one device operation over a list of draw commands:
+//   drawLine        :152-487  Bresenham with its horizontal / vertical cases, Xiaolin Wu with its horizontal case, the thick fast line
+//                             (fillPolygon of four corners, two fillCircle(.fast)), the thick soft line by distance and its axis-aligned form
+//   drawPolygon, drawRectangle :579-601 (drawLine per edge), fillRectangle :608-632, fillPolygon :935-1017
+//   drawCircle, fillCircle :636-644, :752-876, :1021-1084 (drawBresenhamCircle, renderRing, fillCircleFast's spans)
+// composited with Rgba.blend(.normal) and convertColor exactly as Image.insert does (zg_blend.h).
+//
+// The reference's result at a pixel is a fold, in call order, over every write any call makes to that pixel, and blending writes do not
+// commute. So the device gathers: one workgroup per 16 x 16 pixel tile, one lane per pixel. The lane keeps its pixel in registers, walks the
+// command list in order, applies each write that reaches its pixel — as often as the reference makes it — and stores once if anything did.
+//   k_canvas_prep   one lane per command: checks the command against the contract and writes the pixel box that bounds everything the command
+//                   can write (empty for a command that is skipped, draws nothing or lies past the count word)
+//   k_canvas        per tile: 1024 commands at a time, each lane tests four commands' boxes against the tile and the hits are compacted in list
+//                   order (ballot + prefix, no atomics: the order is the list's by construction); then every lane applies the tile's commands.
+//                   A command is expanded into the reference's sequence of internal calls on the fly (a rectangle outline is four lines, a thick
+//                   fast line a polygon and two discs ...), so no expanded list and no per-tile list ever exists in memory: the only scratch is the
+//                   8 bytes per command of the boxes, a size the host knows without reading the (device-resident) commands.
+// What is the same for a whole row of a tile — fillPolygon's sorted intersections, fillCircleFast's row value and span, the axis-aligned thick
+// line's coverage — is computed once per (call, row) into LDS by 16 lanes.
+// The sequential recurrences are evaluated per pixel without tables (their length depends on commands the host never sees, so a table could
+// only be sized for the worst case, n x 64 edges x 32768 steps): the integer Bresenham line has a closed form (tests/canvas_ref.py holds it to
+// the literal walk); fillCircleFast's `y += 1` in f32 is replayed a binade at a time (exact inside one); Wu's `intery += gradient` and the
+// Bresenham circle are re-walked by each lane up to its own step, after a tile-level test has let through only the tiles near the line or ring.
+#include "zg_internal.h"
+#include "zg_blend.h"
+
+#include <cmath>
+#include <cstring>
+
+#pragma clang fp contract(off)
+
+namespace zg {
+
+constexpr int CV_TILE = 16;
+constexpr int CV_CHUNK = 1024; // commands a workgroup tests against its tile between two barriers
+constexpr float CV_TILE_REACH = 11.4f; // from a tile's centre (7.5, 7.5) to its farthest pixel centre, rounded up
+using Rgba8 = typename Px<ZG_PIXEL_RGBA_U8>::Vec;
+
+// 0: inside the contract; 1: outside it; 2: a polygon of more than ZG_CANVAS_MAX_VERTICES vertices
+__host__ __device__ inline bool cv_coord_ok(float v) { return fabsf(v) <= ZG_CANVAS_MAX_COORD; } // false for NaN and the infinities
+__host__ __device__ inline int cv_check(const zg_draw_cmd &c, const float *vertices, uint32_t n_vertices) {
+    if (c.kind < ZG_DRAW_LINE || c.kind > ZG_DRAW_FILL_POLYGON || (c.mode != ZG_DRAW_FAST && c.mode != ZG_DRAW_SOFT)) return 1;
+    if (c.width > ZG_CANVAS_MAX_WIDTH) return 1;
+    if (c.kind == ZG_DRAW_POLYGON || c.kind == ZG_DRAW_FILL_POLYGON) {
+        if (c.n_vertices > ZG_CANVAS_MAX_VERTICES) return 2;
+        if (c.first_vertex > n_vertices || c.n_vertices > n_vertices - c.first_vertex) return 1;
+        for (uint32_t i = 0; i < c.n_vertices; ++i)
+            if (!cv_coord_ok(vertices[2 * (size_t)(c.first_vertex + i)]) || !cv_coord_ok(vertices[2 * (size_t)(c.first_vertex + i) + 1])) return 1;
+        return 0;
+    }
+    const int np = (c.kind == ZG_DRAW_CIRCLE || c.kind == ZG_DRAW_FILL_CIRCLE) ? 3 : 4;
+    for (int i = 0; i < np; ++i)
+        if (!cv_coord_ok(c.p[i])) return 1;
+    return 0;
+}
+
+// How far from the segment a drawLine can write: half the width, the roundings of end points and spans, and for a Wu line the drift of
+// `intery += gradient` (at most half an ulp per step: steps * largest magnitude * 2^-24, taken twice over).
+__device__ inline float cv_line_pad(float x1, float y1, float x2, float y2, uint32_t width, int mode) {
+    float pad = 0.5f * (float)width + 3.0f;
+    if (mode == ZG_DRAW_SOFT && width == 1) {
+        const float extent = fmaxf(fabsf(x2 - x1), fabsf(y2 - y1)) + 2.0f;
+        const float largest = fmaxf(fmaxf(fabsf(x1), fabsf(y1)), fmaxf(fabsf(x2), fabsf(y2))) + 2.0f;
+        pad += extent * largest * (1.0f / 8388608.0f);
+    }
+    return pad;
+}
+
+__global__ __launch_bounds__(256) void k_canvas_prep(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices,
+                                                     uint32_t n_vertices, int rows, int cols, ushort4 *boxes) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t count = count_device ? min(*count_device, n) : n;
+    int4 box = make_int4(0, 0, 0, 0);
+    if (i < count && cv_check(cmds[i], vertices, n_vertices) == 0) {
+        const zg_draw_cmd c = cmds[i];
+        float x0 = 0, y0 = 0, x1 = 0, y1 = 0, pad = 0;
+        bool draws = true;
+        switch (c.kind) {
+        case ZG_DRAW_LINE:
+            x0 = fminf(c.p[0], c.p[2]); x1 = fmaxf(c.p[0], c.p[2]); y0 = fminf(c.p[1], c.p[3]); y1 = fmaxf(c.p[1], c.p[3]);
+            pad = cv_line_pad(x0, y0, x1, y1, c.width, c.mode);
+            draws = c.width != 0;
+            break;
+        case ZG_DRAW_RECT:
+            x0 = fminf(c.p[0], c.p[2] - 1); x1 = fmaxf(c.p[0], c.p[2] - 1); y0 = fminf(c.p[1], c.p[3] - 1); y1 = fmaxf(c.p[1], c.p[3] - 1);
+            pad = cv_line_pad(x0, y0, x1, y1, c.width, c.mode);
+            draws = c.width != 0;
+            break;
+        case ZG_DRAW_FILL_RECT:
+            x0 = fminf(c.p[0], c.p[2]); x1 = fmaxf(c.p[0], c.p[2]); y0 = fminf(c.p[1], c.p[3]); y1 = fmaxf(c.p[1], c.p[3]);
+            pad = 1.0f;
+            break;
+        case ZG_DRAW_CIRCLE:
+        case ZG_DRAW_FILL_CIRCLE:
+            x0 = c.p[0] - c.p[2]; x1 = c.p[0] + c.p[2]; y0 = c.p[1] - c.p[2]; y1 = c.p[1] + c.p[2];
+            pad = (c.kind == ZG_DRAW_CIRCLE ? 0.5f * (float)c.width : 0.0f) + 3.0f;
+            draws = c.p[2] > 0 && (c.kind == ZG_DRAW_FILL_CIRCLE || c.width != 0);
+            break;
+        default: { // the polygons
+            draws = c.kind == ZG_DRAW_POLYGON ? (c.width != 0 && c.n_vertices != 0) : c.n_vertices >= 3;
+            if (draws) {
+                const float *v = vertices + 2 * (size_t)c.first_vertex;
+                x0 = x1 = v[0]; y0 = y1 = v[1];
+                for (uint32_t k = 1; k < c.n_vertices; ++k) {
+                    x0 = fminf(x0, v[2 * k]); x1 = fmaxf(x1, v[2 * k]); y0 = fminf(y0, v[2 * k + 1]); y1 = fmaxf(y1, v[2 * k + 1]);
+                }
+                pad = c.kind == ZG_DRAW_POLYGON ? cv_line_pad(x0, y0, x1, y1, c.width, c.mode) : 2.0f;
+            }
+        }
+        }
+        if (draws) {
+            const float fc = (float)cols, fr = (float)rows;
+            box.x = (int)fminf(fmaxf(floorf(x0 - pad), 0.0f), fc);
+            box.y = (int)fminf(fmaxf(floorf(y0 - pad), 0.0f), fr);
+            box.z = (int)fminf(fmaxf(ceilf(x1 + pad) + 1.0f, 0.0f), fc);
+            box.w = (int)fminf(fmaxf(ceilf(y1 + pad) + 1.0f, 0.0f), fr);
+            if (box.x >= box.z || box.y >= box.w) box = make_int4(0, 0, 0, 0);
+        }
+    }
+    boxes[i] = make_ushort4((unsigned short)box.x, (unsigned short)box.y, (unsigned short)box.z, (unsigned short)box.w); // 0 .. 32768 each
+}
+
+// Is the segment p1-p2 farther than `limit` from (cx, cy)? f32 with margins to spare: the callers' limits carry whole pixels of slack.
+__device__ inline bool cv_far_from_segment(float cx, float cy, float p1x, float p1y, float p2x, float p2y, float limit) {
+    const float dx = p2x - p1x, dy = p2y - p1y, len2 = dx * dx + dy * dy;
+    float t = len2 > 0 ? ((cx - p1x) * dx + (cy - p1y) * dy) / len2 : 0.0f;
+    t = fmaxf(0.0f, fminf(t, 1.0f));
+    const float qx = cx - (p1x + t * dx), qy = cy - (p1y + t * dy);
+    return sqrtf(qx * qx + qy * qy) > limit;
+}
+// Can the command write into the tile at (tx0, ty0)? Exact "no", generous "yes": for a line the distance from the tile's centre to the
+// segment, for a circle to the ring; the other kinds fill most of their boxes. One lane per command asks this while the tile's list is
+// made; a line or ring that is part of a larger command (an edge of a rectangle or polygon) is asked again by all lanes when it is drawn.
+__device__ inline bool cv_tile_may_touch(const zg_draw_cmd &c, int tx0, int ty0) {
+    const float tcx = (float)tx0 + 7.5f, tcy = (float)ty0 + 7.5f;
+    if (c.kind == ZG_DRAW_LINE)
+        return !cv_far_from_segment(tcx, tcy, c.p[0], c.p[1], c.p[2], c.p[3], cv_line_pad(c.p[0], c.p[1], c.p[2], c.p[3], c.width, c.mode) + CV_TILE_REACH + 0.5f);
+    if (c.kind == ZG_DRAW_CIRCLE || c.kind == ZG_DRAW_FILL_CIRCLE) {
+        const float dx = tcx - c.p[0], dy = tcy - c.p[1], dc = sqrtf(dx * dx + dy * dy);
+        const float half = c.kind == ZG_DRAW_CIRCLE ? 0.5f * (float)c.width : 0.0f;
+        if (dc - CV_TILE_REACH > c.p[2] + half + 3.0f) return false;
+        return !(c.kind == ZG_DRAW_CIRCLE && dc + CV_TILE_REACH < c.p[2] - half - 3.0f);
+    }
+    return true;
+}
+
+__device__ inline float cv_clamp(float v, float lo, float hi) { return fmaxf(lo, fminf(v, hi)); } // std.math.clamp
+__device__ inline Rgba8 cv_fade(Rgba8 c, float alpha) { // Rgba(u8).fade (color.zig:447-456)
+    c[3] = (uint8_t)(int)truncf((float)c[3] * cv_clamp(alpha, 0.0f, 1.0f));
+    return c;
+}
+__device__ inline float cv_fpart(float x) { return x - floorf(x); }
+__device__ inline float cv_rfpart(float x) { return 1.0f - cv_fpart(x); }
+
+// One lane's view of the canvas: its pixel in registers and the reference's drawing routines, each reduced to "does this call write my
+// pixel, and with what". Routines that use LDS or a barrier (poly_fill, disc_fast, the axis-aligned line and their callers) are entered by all 256 lanes of the workgroup
+// together: every branch around them depends on the command and the tile only.
+template <int PIX> struct Cv {
+    using P = Px<PIX>;
+    typename P::Vec px;
+    bool dirty, inside;
+    int col, row, tx0, ty0, tid;
+    float fx, fy, fcols, frows;
+    float *s_vx, *s_vy, *s_ix; // polygon vertices [64], [64]; sorted intersections [16][64]
+    float *s_row;              // what a disc or an axis-aligned line computes once per tile row or column [16][3]
+    int *s_icnt;               // intersections per tile row [16]
+
+    __device__ void solid(Rgba8 c) { // dest.* = convertColor(T, color)
+        if (!inside) return;
+        px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
+        dirty = true;
+    }
+    // setPixel with an Rgba colour (:504-514): it hands assignPixel (image.zig:67-94) convertColor(T, color), so only an Rgba destination still
+    // has an Rgba sample to blend (when a != 255). On u8 and Rgb the converted sample has lost its alpha and is stored whatever the alpha was,
+    // a faded alpha of 0 included.
+    __device__ void pixel(Rgba8 c) {
+        if (!inside) return;
+        if constexpr (PIX == ZG_PIXEL_RGBA_U8) {
+            if (c[3] != 255) blend_u8(px, c, 1); else px = c;
+        } else {
+            px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
+        }
+        dirty = true;
+    }
+    __device__ void point(float x, float y, Rgba8 c) { // setPoint (:518-523)
+        if (floorf(x) == fx && floorf(y) == fy) pixel(c);
+    }
+    __device__ void span(float x1, float x2, float y, Rgba8 c) { // setHorizontalSpan (:129-145)
+        if (y < 0 || y >= frows) return;
+        if (x2 < 0 || x1 >= fcols) return;
+        const int r = (int)y, start = (int)fmaxf(0.0f, floorf(x1)), end = (int)fminf(fcols - 1, ceilf(x2));
+        if (r == row && col >= start && col <= end) solid(c);
+    }
+    // clampRectToImage (:62-79)
+    __device__ bool clamp_rect(float l, float t, float r, float b, int &left, int &top, int &right, int &bottom) const {
+        left = (int)cv_clamp(l, 0.0f, fcols); top = (int)cv_clamp(t, 0.0f, frows);
+        right = (int)cv_clamp(r, 0.0f, fcols); bottom = (int)cv_clamp(b, 0.0f, frows);
+        return !(left >= right || top >= bottom);
+    }
+    __device__ float tile_distance(float cx, float cy) const { // from the tile's centre to (cx, cy)
+        const float dx = (float)tx0 + 7.5f - cx, dy = (float)ty0 + 7.5f - cy;
+        return sqrtf(dx * dx + dy * dy);
+    }
+
+    __device__ void fill_rect(float l, float t, float r, float b, Rgba8 color, int mode) { // :608-632
+        int left, top, right, bottom;
+        if (!clamp_rect(l, t, r, b, left, top, right, bottom)) return;
+        if (col < left || col >= right || row < top || row >= bottom) return;
+        if (mode == ZG_DRAW_FAST) solid(color); else pixel(color);
+    }
+
+    // renderRing over the full circle (:794-822) with ringBoundingBox and ringCoverage (:754-786)
+    __device__ void ring(float cx, float cy, float inner, float outer, Rgba8 color, int mode) {
+        const float dc = tile_distance(cx, cy);
+        if (dc - CV_TILE_REACH > outer + 3.0f || (inner > 0 && dc + CV_TILE_REACH < inner - 3.0f)) return; // the tile misses the ring
+        const int left = (int)roundf(cv_clamp(cx - outer - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - outer - 1, 0.0f, frows));
+        const int right = (int)roundf(cv_clamp(cx + outer + 1, 0.0f, fcols)), bottom = (int)roundf(cv_clamp(cy + outer + 1, 0.0f, frows));
+        if (left >= right || top >= bottom) return;
+        if (col < left || col >= right || row < top || row >= bottom) return;
+        const float y = fy - cy, x = fx - cx;
+        const float dist_sq = x * x + y * y;
+        if (mode == ZG_DRAW_SOFT) {
+            const float dist = sqrtf(dist_sq);
+            if (dist > outer + 0.5f) return;
+            if (inner > 0 && dist < inner - 0.5f) return;
+            float alpha = 1.0f;
+            if (dist > outer - 0.5f) alpha = fminf(alpha, outer + 0.5f - dist);
+            if (inner > 0 && dist < inner + 0.5f) alpha = fminf(alpha, dist - (inner - 0.5f));
+            const float coverage = cv_clamp(alpha, 0.0f, 1.0f);
+            if (coverage <= 0) return;
+            pixel(cv_fade(color, coverage));
+        } else {
+            const bool inside_outer = dist_sq <= outer * outer;
+            const bool outside_inner = inner <= 0 || dist_sq >= inner * inner;
+            if (inside_outer && outside_inner) solid(color);
+        }
+    }
+
+    // drawBresenhamCircle over the full circle (:826-860): f32 state that only ever holds integers. The step (x, y) that can reach this
+    // pixel is fixed by the pixel (x = the larger, y = the smaller of its |offsets|); the lane walks to it, then makes the step's eight
+    // setPoint calls in their order, so a pixel that two of the offsets name (y == 0, x == y) is written twice.
+    __device__ void circle_bresenham(float center_x, float center_y, float radius, Rgba8 color) {
+        const float cx = roundf(center_x), cy = roundf(center_y), r = roundf(radius);
+        const float dc = tile_distance(cx, cy);
+        if (dc - CV_TILE_REACH > r + 2.0f || dc + CV_TILE_REACH < r - 2.0f) return;
+        const float ox = fx - cx, oy = fy - cy;
+        const float a = fmaxf(fabsf(ox), fabsf(oy)), b = fminf(fabsf(ox), fabsf(oy));
+        float x = r, y = 0, err = 0;
+        bool hit = false;
+        while (x >= y) {
+            if (y > b) break;
+            if (y == b && x == a) { hit = true; break; }
+            if (err <= 0) { y += 1; err += 2 * y + 1; }
+            if (err > 0) { x -= 1; err -= 2 * x + 1; }
+        }
+        if (!hit) return;
+        if (x == ox && y == oy) pixel(color);
+        if (-x == ox && y == oy) pixel(color);
+        if (x == ox && -y == oy) pixel(color);
+        if (-x == ox && -y == oy) pixel(color);
+        if (y == ox && x == oy) pixel(color);
+        if (-y == ox && x == oy) pixel(color);
+        if (y == ox && -x == oy) pixel(color);
+        if (-y == ox && -x == oy) pixel(color);
+    }
+
+    // fillCircleFast (:1067-1084): y starts at top = max(0, cy - radius) and grows by `y += 1` in f32. Adding 1 is exact while y stays inside
+    // a binade and rounds only when it crosses a power of two, so the lane replays the walk a binade at a time up to its own row
+    // (tests/canvas_ref.py: disc_row_y, held to the literal walk): y is the walk's value in this row, if it has one. The row's y and span
+    // ends are the same for the whole row: lanes 0-15 compute them once per (disc, tile row) into LDS. Entered by all lanes together.
+    __device__ void disc_fast(float cx, float cy, float radius, Rgba8 color) {
+        if (tile_distance(cx, cy) - CV_TILE_REACH > radius + 3.0f) return;
+        if (tid < CV_TILE) {
+            const int r = ty0 + tid;
+            const float top = fmaxf(0.0f, cy - radius), bottom = fminf(frows - 1, cy + radius);
+            float y = top;
+            while (y <= bottom) {
+                const int t = (int)y;
+                if (t >= r) break;
+                if (y < 1.0f) { y = y + 1.0f; continue; }
+                const float next_pow2 = __uint_as_float(((__float_as_uint(y) >> 23) + 1u) << 23);
+                const int exact = (int)ceilf(next_pow2 - y) - 1; // steps that stay below it (the difference is exact)
+                const int steps = min(exact, r - t);
+                y = steps > 0 ? y + (float)steps : y + 1.0f;
+            }
+            float x1 = 0.0f, x2 = 0.0f;
+            bool has_span = y <= bottom && (int)y == r;
+            if (has_span) {
+                const float dy = y - cy;
+                const float dx = sqrtf(fmaxf(0.0f, radius * radius - dy * dy));
+                has_span = dx > 0;
+                x1 = cx - dx; x2 = cx + dx;
+            }
+            s_row[3 * tid] = has_span ? y : -1.0f; // y >= 0 whenever the row has a span
+            s_row[3 * tid + 1] = x1;
+            s_row[3 * tid + 2] = x2;
+        }
+        __syncthreads();
+        const float y = s_row[3 * (tid >> 4)];
+        if (y >= 0) span(s_row[3 * (tid >> 4) + 1], s_row[3 * (tid >> 4) + 2], y, color);
+        __syncthreads();
+    }
+
+    // fillPolygon (:935-1017) of the n >= 3 vertices in s_vx / s_vy. Lanes 0-15 each take one row of the tile: the intersections in the
+    // reference's formula and edge rule, sorted ascending; then every lane reads its row's spans in pairs, left to right.
+    __device__ void poly_fill(int n, Rgba8 color, int mode) {
+        __syncthreads();
+        if (tid < CV_TILE) {
+            const float y = (float)(ty0 + tid);
+            float min_y = s_vy[0], max_y = s_vy[0];
+            for (int i = 1; i < n; ++i) { min_y = fminf(min_y, s_vy[i]); max_y = fmaxf(max_y, s_vy[i]); }
+            const float start_y = fmaxf(0.0f, floorf(min_y)), end_y = fminf(frows - 1, ceilf(max_y));
+            float *xs = s_ix + tid * 64;
+            int count = 0;
+            if (y >= start_y && y <= end_y) {
+                for (int i = 0; i < n; ++i) {
+                    const int j = i + 1 == n ? 0 : i + 1;
+                    const float p1x = s_vx[i], p1y = s_vy[i], p2x = s_vx[j], p2y = s_vy[j];
+                    if ((p1y <= y && p2y > y) || (p2y <= y && p1y > y)) {
+                        const float x = p1x + (y - p1y) * (p2x - p1x) / (p2y - p1y);
+                        int k = count++;
+                        for (; k > 0 && xs[k - 1] > x; --k) xs[k] = xs[k - 1];
+                        xs[k] = x;
+                    }
+                }
+            }
+            s_icnt[tid] = count;
+        }
+        __syncthreads();
+        const int count = s_icnt[tid >> 4];
+        const float *xs = s_ix + (tid >> 4) * 64;
+        for (int i = 0; i + 1 < count; i += 2) {
+            const float left_edge = xs[i], right_edge = xs[i + 1];
+            if (mode == ZG_DRAW_SOFT) {
+                const float x = fx, x_start = fmaxf(0.0f, floorf(left_edge)), x_end = fminf(fcols - 1, ceilf(right_edge));
+                if (x >= x_start && x <= x_end) {
+                    float alpha = 1.0f;
+                    if (x < left_edge + 1) alpha = fminf(alpha, x + 0.5f - left_edge);
+                    if (x > right_edge - 1) alpha = fminf(alpha, right_edge - (x - 0.5f));
+                    alpha = cv_clamp(alpha, 0.0f, 1.0f);
+                    if (alpha > 0) pixel(cv_fade(color, alpha));
+                }
+            } else {
+                span(left_edge, right_edge, fy, color);
+            }
+        }
+        __syncthreads();
+    }
+
+    // drawLineBresenham (:187-240)
+    __device__ void line_bresenham(float p1x, float p1y, float p2x, float p2y, Rgba8 color) {
+        const int x1 = (int)p1x, y1 = (int)p1y, x2 = (int)p2x, y2 = (int)p2y;
+        if (y1 == y2) {
+            span((float)min(x1, x2), (float)max(x1, x2), (float)y1, color);
+            return;
+        }
+        if (x1 == x2) {
+            if (col == x1 && row >= min(y1, y2) && row <= max(y1, y2)) solid(color);
+            return;
+        }
+        // The general walk takes one major-axis step per iteration; after m of them it has taken floor((2 m dmin + dmaj - 1) / (2 dmaj))
+        // minor-axis steps (tests/test_canvas_oracle.py compares this with the literal walk for every (dx, dy) up to 64 in all octants).
+        const int dx = abs(x2 - x1), dy = abs(y2 - y1);
+        const int sx = x1 < x2 ? 1 : -1, sy = y1 < y2 ? 1 : -1;
+        const int mx = (col - x1) * sx, my = (row - y1) * sy;
+        if (mx < 0 || mx > dx || my < 0 || my > dy) return;
+        if (dx >= dy) {
+            if ((long long)my == (2ll * mx * dy + dx - 1) / (2ll * dx)) solid(color);
+        } else {
+            if ((long long)mx == (2ll * my * dx + dy - 1) / (2ll * dy)) solid(color);
+        }
+    }
+
+    // drawLineXiaolinWu (:246-341): end point 1 (two pixels), end point 2 (two pixels), then the main loop's two pixels of this lane's column
+    // (row, when steep), each applied when it names this pixel — a line whose end points round to one column blends that column twice.
+    __device__ void line_wu(float x1, float y1, float x2, float y2, Rgba8 c2) {
+        if (fabsf(y2 - y1) < 0.01f) {
+            const float y = roundf(y1), min_x = fminf(x1, x2), max_x = fmaxf(x1, x2);
+            const float left_x = floorf(min_x), right_x = ceilf(max_x);
+            if (min_x > left_x) point(left_x, y, cv_fade(c2, min_x - left_x));
+            const float solid_start = ceilf(min_x), solid_end = floorf(max_x);
+            if (solid_end >= solid_start) span(solid_start, solid_end, y, c2);
+            if (max_x < right_x) point(right_x, y, cv_fade(c2, right_x - max_x));
+            return;
+        }
+        const bool steep = fabsf(y2 - y1) > fabsf(x2 - x1);
+        if (steep) { float t = x1; x1 = y1; y1 = t; t = x2; x2 = y2; y2 = t; }
+        if (x1 > x2) { float t = x1; x1 = x2; x2 = t; t = y1; y1 = y2; y2 = t; }
+        const float dx = x2 - x1, dy = y2 - y1;
+        const float gradient = dx == 0 ? 1.0f : dy / dx;
+        const float major = steep ? fy : fx; // this pixel along the line's major axis
+        float x_px1, x_px2, intery;
+        {
+            const float x_end = roundf(x1), y_end = y1 + gradient * (x_end - x1), x_gap = cv_rfpart(x1 + 0.5f), y_px = floorf(y_end);
+            if (steep) { point(y_px, x_end, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            else { point(x_end, y_px, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            x_px1 = x_end;
+            intery = y_end + gradient;
+        }
+        {
+            const float x_end = roundf(x2), y_end = y2 + gradient * (x_end - x2), x_gap = cv_fpart(x2 + 0.5f), y_px = floorf(y_end);
+            if (steep) { point(y_px, x_end, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            else { point(x_end, y_px, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            x_px2 = x_end;
+        }
+        if (!(major > x_px1 && major < x_px2)) return;
+        const int steps = (int)(major - x_px1) - 1; // additions before the loop reaches this column
+        for (int k = 0; k < steps; ++k) intery += gradient;
+        if (steep) { point(intery, major, cv_fade(c2, cv_rfpart(intery))); point(floorf(intery) + 1, major, cv_fade(c2, cv_fpart(intery))); }
+        else { point(major, intery, cv_fade(c2, cv_rfpart(intery))); point(major, floorf(intery) + 1, cv_fade(c2, cv_fpart(intery))); }
+    }
+
+    __device__ static float perpendicular_alpha(float sample, float center, float half_width) { // :491-496
+        const float dist = fabsf(sample - center);
+        if (dist > half_width + 0.5f) return 0.0f;
+        if (dist > half_width - 0.5f) return half_width + 0.5f - dist;
+        return 1.0f;
+    }
+
+    // drawLine (:152-181) and everything under it
+    __device__ void line(float p1x, float p1y, float p2x, float p2y, Rgba8 color, uint32_t width, int mode) {
+        { // the tile against the segment: nothing the line writes is farther from it than `pad`
+            const float pad = cv_line_pad(p1x, p1y, p2x, p2y, width, mode);
+            if (cv_far_from_segment((float)tx0 + 7.5f, (float)ty0 + 7.5f, p1x, p1y, p2x, p2y, pad + CV_TILE_REACH + 0.5f)) return;
+        }
+        const float half_width = (float)width / 2.0f;
+        if (mode == ZG_DRAW_FAST) {
+            if (width == 1) { line_bresenham(p1x, p1y, p2x, p2y, color); return; }
+            // drawLineRectangle (:347-381)
+            const float dx = p2x - p1x, dy = p2y - p1y;
+            const float line_length = sqrtf(dx * dx + dy * dy);
+            if (line_length == 0) { disc_fast(p1x, p1y, half_width, color); return; }
+            const float perp_x = -dy / line_length * half_width, perp_y = dx / line_length * half_width;
+            if (tid == 0) {
+                s_vx[0] = p1x - perp_x; s_vy[0] = p1y - perp_y;
+                s_vx[1] = p1x + perp_x; s_vy[1] = p1y + perp_y;
+                s_vx[2] = p2x + perp_x; s_vy[2] = p2y + perp_y;
+                s_vx[3] = p2x - perp_x; s_vy[3] = p2y - perp_y;
+            }
+            poly_fill(4, color, ZG_DRAW_FAST);
+            disc_fast(p1x, p1y, half_width, color);
+            disc_fast(p2x, p2y, half_width, color);
+            return;
+        }
+        if (width == 1) { line_wu(p1x, p1y, p2x, p2y, color); return; }
+        // drawLineDistance (:387-437)
+        const float dx = p2x - p1x, dy = p2y - p1y;
+        const float length_sq = dx * dx + dy * dy;
+        if (length_sq == 0) { ring(p1x, p1y, 0.0f, half_width, color, ZG_DRAW_SOFT); return; }
+        int left, top, right, bottom;
+        if (dx == 0 || dy == 0) { // drawAxisAlignedThickLine (:443-487)
+            const bool is_horizontal = p1y == p2y;
+            const bool ok = is_horizontal ? clamp_rect(fminf(p1x, p2x), p1y - half_width, fmaxf(p1x, p2x) + 1, p1y + half_width + 1, left, top, right, bottom)
+                                          : clamp_rect(p1x - half_width, fminf(p1y, p2y), p1x + half_width + 1, fmaxf(p1y, p2y) + 1, left, top, right, bottom);
+            // the coverage is the same along a row (horizontal) or a column (vertical) of the tile: once per row or column, by lanes 0-15
+            if (tid < CV_TILE) s_row[tid] = is_horizontal ? perpendicular_alpha((float)(ty0 + tid), p1y, half_width) : perpendicular_alpha((float)(tx0 + tid), p1x, half_width);
+            __syncthreads();
+            const float alpha = s_row[is_horizontal ? tid >> 4 : tid & 15];
+            __syncthreads();
+            if (ok && col >= left && col < right && row >= top && row < bottom) {
+                if (alpha > 0) {
+                    if (is_horizontal && alpha >= 1.0f && color[3] == 255) solid(color); // setHorizontalSpan over the box's columns
+                    else pixel(cv_fade(color, alpha));
+                }
+            }
+            ring(p1x, p1y, 0.0f, half_width, color, ZG_DRAW_SOFT);
+            ring(p2x, p2y, 0.0f, half_width, color, ZG_DRAW_SOFT);
+            return;
+        }
+        const float inv_length_sq = 1.0f / length_sq;
+        if (!clamp_rect(fminf(p1x, p2x) - half_width, fminf(p1y, p2y) - half_width, fmaxf(p1x, p2x) + half_width + 1, fmaxf(p1y, p2y) + half_width + 1,
+                        left, top, right, bottom)) return;
+        if (col < left || col >= right || row < top || row >= bottom) return;
+        const float dpx = fx - p1x, dpy = fy - p1y;
+        const float t = cv_clamp((dpx * dx + dpy * dy) * inv_length_sq, 0.0f, 1.0f);
+        const float dist_x = dpx - t * dx, dist_y = dpy - t * dy;
+        const float dist = sqrtf(dist_x * dist_x + dist_y * dist_y);
+        if (dist > half_width + 0.5f) return;
+        float alpha = 1.0f;
+        if (dist > half_width - 0.5f) alpha = half_width + 0.5f - dist;
+        if (alpha > 0) pixel(cv_fade(color, alpha));
+    }
+
+    // One command: the reference's public call
+    __device__ void apply(const zg_draw_cmd &c, const float *vertices) {
+        Rgba8 color;
+        color[0] = c.color[0]; color[1] = c.color[1]; color[2] = c.color[2]; color[3] = c.color[3];
+        switch (c.kind) {
+        case ZG_DRAW_LINE:
+            if (c.width) line(c.p[0], c.p[1], c.p[2], c.p[3], color, c.width, c.mode);
+            break;
+        case ZG_DRAW_RECT: { // :590-601
+            if (!c.width) break;
+            const float l = c.p[0], t = c.p[1], r = c.p[2] - 1, b = c.p[3] - 1;
+            line(l, t, r, t, color, c.width, c.mode);
+            line(r, t, r, b, color, c.width, c.mode);
+            line(r, b, l, b, color, c.width, c.mode);
+            line(l, b, l, t, color, c.width, c.mode);
+            break;
+        }
+        case ZG_DRAW_FILL_RECT:
+            fill_rect(c.p[0], c.p[1], c.p[2], c.p[3], color, c.mode);
+            break;
+        case ZG_DRAW_CIRCLE: { // :636-644, :863-876
+            if (!(c.p[2] > 0) || !c.width) break;
+            if (c.mode == ZG_DRAW_FAST && c.width == 1) { circle_bresenham(c.p[0], c.p[1], c.p[2], color); break; }
+            const float line_width = (float)c.width;
+            ring(c.p[0], c.p[1], c.p[2] - line_width / 2.0f, c.p[2] + line_width / 2.0f, color, c.mode);
+            break;
+        }
+        case ZG_DRAW_FILL_CIRCLE: // :1021-1029
+            if (!(c.p[2] > 0)) break;
+            if (c.mode == ZG_DRAW_SOFT) ring(c.p[0], c.p[1], 0.0f, c.p[2], color, ZG_DRAW_SOFT);
+            else disc_fast(c.p[0], c.p[1], c.p[2], color);
+            break;
+        case ZG_DRAW_POLYGON: { // :579-587
+            if (!c.width) break;
+            const float *v = vertices + 2 * (size_t)c.first_vertex;
+            for (uint32_t i = 0; i < c.n_vertices; ++i) {
+                const uint32_t j = i + 1 == c.n_vertices ? 0 : i + 1;
+                line(v[2 * i], v[2 * i + 1], v[2 * j], v[2 * j + 1], color, c.width, c.mode);
+            }
+            break;
+        }
+        case ZG_DRAW_FILL_POLYGON: {
+            if (c.n_vertices < 3) break;
+            if (tid < (int)c.n_vertices) {
+                s_vx[tid] = vertices[2 * (size_t)(c.first_vertex + tid)];
+                s_vy[tid] = vertices[2 * (size_t)(c.first_vertex + tid) + 1];
+            }
+            poly_fill((int)c.n_vertices, color, c.mode);
+            break;
+        }
+        }
+    }
+};
+
+template <int PIX>
+__global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, const ushort4 *boxes) {
+    using P = Px<PIX>;
+    __shared__ uint16_t s_list[CV_CHUNK];
+    __shared__ int s_wave_count[CV_CHUNK / 64];
+    __shared__ float s_vx[ZG_CANVAS_MAX_VERTICES], s_vy[ZG_CANVAS_MAX_VERTICES], s_ix[CV_TILE * ZG_CANVAS_MAX_VERTICES];
+    __shared__ float s_row[CV_TILE * 3];
+    __shared__ int s_icnt[CV_TILE];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    Cv<PIX> cv;
+    cv.tid = tid;
+    cv.tx0 = (int)blockIdx.x * CV_TILE; cv.ty0 = (int)blockIdx.y * CV_TILE;
+    cv.col = cv.tx0 + (tid & 15); cv.row = cv.ty0 + (tid >> 4);
+    cv.fx = (float)cv.col; cv.fy = (float)cv.row; cv.fcols = (float)img.cols; cv.frows = (float)img.rows;
+    cv.inside = cv.col < img.cols && cv.row < img.rows;
+    cv.dirty = false;
+    cv.px = P::zero();
+    cv.s_vx = s_vx; cv.s_vy = s_vy; cv.s_ix = s_ix; cv.s_icnt = s_icnt; cv.s_row = s_row;
+    const size_t index = (size_t)cv.row * img.stride + (size_t)cv.col;
+    bool loaded = false;
+    // CV_CHUNK commands at a time, in CV_CHUNK / 256 slices of 256 (slice j: commands base + 256 j + tid): one pair of barriers per chunk
+    for (uint32_t base = 0; base < n; base += CV_CHUNK) {
+        bool hit[CV_CHUNK / 256];
+        unsigned long long ballot[CV_CHUNK / 256];
+#pragma unroll
+        for (int j = 0; j < CV_CHUNK / 256; ++j) {
+            const uint32_t i = base + 256u * j + (uint32_t)tid;
+            hit[j] = false;
+            if (i < n) {
+                const ushort4 b = boxes[i];
+                hit[j] = (int)b.x < cv.tx0 + CV_TILE && (int)b.z > cv.tx0 && (int)b.y < cv.ty0 + CV_TILE && (int)b.w > cv.ty0;
+                if (hit[j]) hit[j] = cv_tile_may_touch(cmds[i], cv.tx0, cv.ty0); // lines and circles: the box is mostly empty
+            }
+            ballot[j] = __ballot(hit[j]);
+            if (lane == 0) s_wave_count[4 * j + wave] = __popcll(ballot[j]);
+        }
+        __syncthreads();
+        int total = 0; // list position = the commands of earlier slices, then of earlier waves of this slice, then of earlier lanes
+#pragma unroll
+        for (int j = 0; j < CV_CHUNK / 256; ++j) {
+            int before = total;
+            for (int w = 0; w < 4; ++w) {
+                const int cnt = s_wave_count[4 * j + w];
+                if (w < wave) before += cnt;
+                total += cnt;
+            }
+            if (hit[j]) s_list[before + __popcll(ballot[j] & ((1ull << lane) - 1ull))] = (uint16_t)(256 * j + tid);
+        }
+        __syncthreads();
+        if (total > 0 && !loaded) {
+            if (cv.inside) cv.px = P::load(img.data, index);
+            loaded = true;
+        }
+        for (int k = 0; k < total; ++k) {
+            const uint32_t ci = base + (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[k]);
+            cv.apply(cmds[ci], vertices);
+        }
+        __syncthreads();
+    }
+    if (cv.dirty && cv.inside) P::store(img.data, index, cv.px);
+}
+
+template <typename T> __global__ __launch_bounds__(256) void k_canvas_build(const T *list, const uint32_t *count, uint32_t capacity, float radius, uint32_t color,
+                                                                            uint32_t width, int mode, zg_draw_cmd *out, uint32_t *count_out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t m = min(*count, capacity);
+    if (i == 0) *count_out = m;
+    if (i >= m) return;
+    zg_draw_cmd c;
+    c.mode = mode; c.width = width;
+    c.color[0] = (uint8_t)color; c.color[1] = (uint8_t)(color >> 8); c.color[2] = (uint8_t)(color >> 16); c.color[3] = (uint8_t)(color >> 24);
+    c.first_vertex = 0; c.n_vertices = 0;
+    if constexpr (std::is_same<T, zg_hough_line>::value) {
+        c.kind = ZG_DRAW_LINE;
+        c.p[0] = list[i].p1[0]; c.p[1] = list[i].p1[1]; c.p[2] = list[i].p2[0]; c.p[3] = list[i].p2[1];
+    } else {
+        c.kind = ZG_DRAW_CIRCLE;
+        c.p[0] = list[i].x; c.p[1] = list[i].y; c.p[2] = radius; c.p[3] = 0.0f;
+    }
+    out[i] = c;
+}
+
+static int check_canvas_image(const zg_image *img, bool device_pointer) {
+    if (const int rc = check_image(img, "img", device_pointer)) return rc;
+    ZG_REQUIRE(img->pixel == ZG_PIXEL_U8 || img->pixel == ZG_PIXEL_RGB_U8 || img->pixel == ZG_PIXEL_RGBA_U8, ZG_ERR_UNSUPPORTED,
+               "canvas_draw: pixel type %d (u8, Rgb(u8) and Rgba(u8) are drawn on)", img->pixel);
+    ZG_REQUIRE(img->rows <= ZG_CANVAS_MAX_SIZE && img->cols <= ZG_CANVAS_MAX_SIZE, ZG_ERR_UNSUPPORTED, "canvas_draw: %u x %u image (at most %u each way)",
+               img->rows, img->cols, ZG_CANVAS_MAX_SIZE);
+    return ZG_OK;
+}
+
+static int canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
+                       hipStream_t s) {
+    ZG_REQUIRE(n <= ZG_CANVAS_MAX_COMMANDS, ZG_ERR_UNSUPPORTED, "canvas_draw: %u commands (at most %u a call)", n, ZG_CANVAS_MAX_COMMANDS);
+    if (n == 0 || img->rows == 0 || img->cols == 0) return ZG_OK;
+    ScratchBlock sc(s);
+    ushort4 *boxes;
+    sc.take(boxes, n);
+    int rc;
+    if ((rc = sc.alloc())) return rc;
+    k_canvas_prep<<<ceil_div(n, 256), 256, 0, s>>>(cmds, n, count_device, vertices, n_vertices, (int)img->rows, (int)img->cols, boxes);
+    if ((rc = launch_ok("k_canvas_prep"))) return rc;
+    const dim3 grid(ceil_div(img->cols, CV_TILE), ceil_div(img->rows, CV_TILE));
+    const DImg d = dimg(img);
+    switch (img->pixel) {
+    case ZG_PIXEL_U8: k_canvas<ZG_PIXEL_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
+    case ZG_PIXEL_RGB_U8: k_canvas<ZG_PIXEL_RGB_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
+    default: k_canvas<ZG_PIXEL_RGBA_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
+    }
+    return launch_ok("k_canvas");
+}
+
+static int check_builder(const uint32_t *count, const uint8_t *color, uint32_t width, int mode, const uint32_t *count_out, const char *what) {
+    ZG_REQUIRE(count != nullptr && count_out != nullptr && color != nullptr, ZG_ERR_INVALID_ARGUMENT, "%s: null count, count_out or color", what);
+    ZG_REQUIRE(mode == ZG_DRAW_FAST || mode == ZG_DRAW_SOFT, ZG_ERR_INVALID_ARGUMENT, "%s: mode %d", what, mode);
+    ZG_REQUIRE(width <= ZG_CANVAS_MAX_WIDTH, ZG_ERR_INVALID_ARGUMENT, "%s: width %u (at most %u)", what, width, ZG_CANVAS_MAX_WIDTH);
+    return ZG_OK;
+}
+
+} // namespace zg
+
+using namespace zg;
+
+extern "C" {
+
+size_t zg_sizeof_draw_cmd(void) { return sizeof(zg_draw_cmd); }
+uint32_t zg_canvas_tile(void) { return CV_TILE; }
+
+int zg_canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
+                   zg_stream stream) {
+    if (const int rc = check_canvas_image(img, true)) return rc;
+    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
+    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
+    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream));
+}
+
+int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, uint32_t n_vertices) {
+    if (const int rc = check_canvas_image(img, false)) return rc;
+    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
+    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
+    for (uint32_t i = 0; i < n; ++i) {
+        const int bad = cv_check(cmds[i], vertices, n_vertices);
+        ZG_REQUIRE(bad != 2, ZG_ERR_UNSUPPORTED, "canvas_draw: command %u is a polygon of %u vertices (at most %u)", i, cmds[i].n_vertices, ZG_CANVAS_MAX_VERTICES);
+        ZG_REQUIRE(bad == 0, ZG_ERR_INVALID_ARGUMENT,
+                   "canvas_draw: command %u is outside the contract (kind, mode, finite parameters of magnitude <= %g, width <= %u, vertex range)", i,
+                   (double)ZG_CANVAS_MAX_COORD, ZG_CANVAS_MAX_WIDTH);
+    }
+    if (n == 0) return ZG_OK;
+    ScratchBlock sc;
+    zg_draw_cmd *dcmds;
+    float *dvertices;
+    sc.take(dcmds, n);
+    sc.take(dvertices, 2 * (size_t)n_vertices + 1);
+    int rc;
+    if ((rc = sc.alloc())) return rc;
+    if ((rc = upload_pageable(dcmds, cmds, (size_t)n * sizeof(zg_draw_cmd), nullptr))) return rc;
+    if (n_vertices && (rc = upload_pageable(dvertices, vertices, 2 * (size_t)n_vertices * sizeof(float), nullptr))) return rc;
+    return host_in_place(img, true, [&](const zg_image *d) { return canvas_draw(d, dcmds, n, nullptr, dvertices, n_vertices, nullptr); });
+}
+
+int zg_canvas_cmds_from_hough_lines(const zg_hough_line *lines, const uint32_t *counts, uint32_t capacity, const uint8_t *color, uint32_t width, int mode,
+                                    zg_draw_cmd *cmds_out, uint32_t *count_out, zg_stream stream) {
+    if (const int rc = check_builder(counts, color, width, mode, count_out, "canvas_cmds_from_hough_lines")) return rc;
+    ZG_REQUIRE(capacity == 0 || (lines != nullptr && cmds_out != nullptr), ZG_ERR_INVALID_ARGUMENT, "canvas_cmds_from_hough_lines: null lines or cmds_out");
+    uint32_t packed;
+    std::memcpy(&packed, color, 4);
+    k_canvas_build<zg_hough_line><<<ceil_div(capacity ? capacity : 1u, 256), 256, 0, as_stream(stream)>>>(lines, counts + 1, capacity, 0.0f, packed, width, mode, cmds_out,
+                                                                                                    count_out);
+    return launch_ok("k_canvas_build");
+}
+
+int zg_canvas_cmds_from_keypoints(const zg_keypoint *keypoints, const uint32_t *count, uint32_t capacity, float radius, const uint8_t *color, uint32_t width,
+                                  int mode, zg_draw_cmd *cmds_out, uint32_t *count_out, zg_stream stream) {
+    if (const int rc = check_builder(count, color, width, mode, count_out, "canvas_cmds_from_keypoints")) return rc;
+    ZG_REQUIRE(capacity == 0 || (keypoints != nullptr && cmds_out != nullptr), ZG_ERR_INVALID_ARGUMENT, "canvas_cmds_from_keypoints: null keypoints or cmds_out");
+    ZG_REQUIRE(std::fabs(radius) <= ZG_CANVAS_MAX_COORD, ZG_ERR_INVALID_ARGUMENT, "canvas_cmds_from_keypoints: radius %g", (double)radius);
+    uint32_t packed;
+    std::memcpy(&packed, color, 4);
+    k_canvas_build<zg_keypoint><<<ceil_div(capacity ? capacity : 1u, 256), 256, 0, as_stream(stream)>>>(keypoints, count, capacity, radius, packed, width, mode, cmds_out,
+                                                                                                  count_out);
+    return launch_ok("k_canvas_build");
+}
+
+} // extern "C"
