@@ -47,7 +47,10 @@ static uint8_t rgb_to_gray_u8(int32_t r, int32_t g, int32_t b) { /* color.zig:10
     int32_t v = (yr * r + yg * g + yb * b + 32768) >> 16;
     return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
-static float clamp01(float v) { return v < 0 ? 0 : (v > 1 ? 1 : v); }
+/* color.zig:53 `const clamp = std.math.clamp`, which is @max(lower, @min(val, upper)); @min / @max return the other operand when one is NaN,
+ * so clamp(NaN, 0, 1) = @max(0, 1) = 1 and the byte is 255 (color.zig:117, 316-318, 433-436, 1045). A C comparison chain would pass the
+ * NaN on to a float -> integer cast, which is undefined in C. */
+static float clamp01(float v) { return v != v ? 1.0f : (v < 0 ? 0 : (v > 1 ? 1 : v)); }
 static float rgb_to_gray_f32(float r, float g, float b) { /* color.zig:1043-1046 */
     const float y = 0.2126f * r + 0.7152f * g + 0.0722f * b;
     return clamp01(y);
@@ -90,7 +93,7 @@ static int convert_legacy(const zo_image *src, int src_space, const zo_image *ds
                     else if (!sf && df) ((float *)dp)[0] = (float)su[0] / 255.0f;
                     else if (sf && !df) {
                         double v = (double)sfl[0];
-                        v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+                        v = v != v ? 1.0 : (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v)); /* color.zig:117: clamp(NaN, 0, 1) = 1, see clamp01 */
                         ((uint8_t *)dp)[0] = (uint8_t)round(v * 255.0);
                     } else ((float *)dp)[0] = sfl[0];
                 } else if (!sf) { /* colour(u8) -> luminance: fixed-point gray, then .as(Dest) */

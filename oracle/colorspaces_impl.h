@@ -10,7 +10,7 @@
  * (-ffp-contract=off) except std.math.lerp, which IS @mulAdd in Zig's std.
  */
 
-static inline ZT ZN(clampv)(ZT v, ZT lo, ZT hi) { return v < lo ? lo : (v > hi ? hi : v); } /* std.math.clamp */
+static inline ZT ZN(clampv)(ZT v, ZT lo, ZT hi) { return v < lo ? lo : (v > hi ? hi : v); } /* std.math.clamp for every ordered v; a NaN passes through here where @max(lo, @min(v, hi)) gives hi: the kernels (colorspaces.hip: cs_clamp) do the same, the byte step after it (color.c: unit_to_u8) follows the reference, and an f32 destination that a NaN reaches differs from the reference */
 static inline ZT ZN(lerp)(ZT a, ZT b, ZT t) { return ZFMA(b - a, t, a); }                     /* std.math.lerp = @mulAdd(b - a, t, a) */
 static inline ZT ZN(maxv)(ZT a, ZT b) { return a > b ? a : b; }
 static inline ZT ZN(minv)(ZT a, ZT b) { return a < b ? a : b; }

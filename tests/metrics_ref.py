@@ -268,3 +268,56 @@ def sum_inputs(seed: int, n: int = 1 << 20):
         ("scaled_1e-12", rng.random(n) * 1e-12, True),
         ("n_1089", rng.random(1089), True),
     ]
+
+
+# ---- the sequential sum outside ordinary terms: infinities, NaN, overflow, subnormals, ties, 2^53 --------------------------------------
+DOMAIN_SUM_INPUTS = ("inf_in_the_middle", "nan_in_the_middle", "inf_then_minus_inf", "finite_overflow", "subnormal_sum", "subnormal_into_normal",
+                     "every_term_a_tie", "reaches_2^53_in_a_chunk", "chunk_ends_at_2^53-1", "negative_zeros", "alternating_positive_sum")
+DOMAIN_SUM_N = 5 * 4096 + 17
+
+
+def domain_sum_input(name: str, n: int, chunk: int = 4096) -> np.ndarray:
+    """n f64 terms of the named kind (read-only); every kind is defined for every n, 0 and 1 included."""
+    rng = np.random.default_rng(DOMAIN_SUM_INPUTS.index(name) * 7919 + n)
+    tiny = 2.0 ** -1074
+    if name in ("inf_in_the_middle", "nan_in_the_middle"):
+        v = rng.random(n)
+        if n:
+            v[n // 2] = math.inf if name == "inf_in_the_middle" else math.nan
+    elif name == "inf_then_minus_inf":  # inf + -inf: NaN from the second one on
+        v = rng.random(n)
+        if n >= 2:
+            v[n // 3], v[n // 3 + max(1, n // 3)] = math.inf, -math.inf
+    elif name == "finite_overflow":  # every term finite, the sum infinite after a few of them
+        v = (rng.random(n) + 0.5) * 1e308
+    elif name == "subnormal_sum":  # at most 2^20 units of 2^-1074 each: the whole sum stays below 2^36 units, subnormal
+        v = rng.integers(0, 1 << 20, n).astype(np.float64) * tiny
+    elif name == "subnormal_into_normal":  # about 2^41 units each: the sum passes 2^52 units (the smallest normal) after some 2000 terms
+        v = rng.integers(0, 1 << 42, n).astype(np.float64) * tiny
+    elif name == "every_term_a_tie":  # the sum sits in [2^52, 2^53), where one unit is 1: every k + 0.5 is a tie, decided by the sum's parity
+        v = rng.integers(0, 8, n).astype(np.float64) + 0.5
+        if n:
+            v[0] = 2.0 ** 52 + 2.0 ** 20 + 1.0
+    elif name == "reaches_2^53_in_a_chunk":  # 2^53 at term 1000; from there on each + 1.0 is a tie that rounds back to even
+        v = np.ones(n)
+        if n:
+            v[0] = 2.0 ** 53 - 1000.0
+    elif name == "chunk_ends_at_2^53-1":  # the first chunk of `chunk` terms ends one below 2^53, the next term reaches it
+        v = np.ones(n)
+        if n:
+            v[0] = 2.0 ** 53 - float(chunk)
+    elif name == "negative_zeros":
+        v = rng.random(n)
+        v[rng.random(n) < 0.3] = -0.0
+    elif name == "alternating_positive_sum":
+        v = rng.random(n) + 1.0
+        v[1::2] = -rng.random(v[1::2].size)
+    else:
+        raise KeyError(name)
+    v.setflags(write=False)
+    return v
+
+
+def same_bits_nan_class(got: float, want: float) -> bool:
+    """Bit equality of two f64, with every NaN one class."""
+    return (got != got and want != want) or bits(got) == bits(want)

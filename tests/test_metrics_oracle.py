@@ -117,6 +117,41 @@ def test_the_chunk_model_on_edge_inputs():
                 assert serial == 0
 
 
+def test_the_chunk_model_on_infinities_nan_subnormals_ties_and_2_to_the_53():
+    """The kinds tests/test_gpu_metrics.py adds to its SUM_INPUTS, through the model at the library's chunk and at 64: the sum is compared
+    with NaN as a class (the loop's NaN and the model's may differ in sign or payload)."""
+    n = R.DOMAIN_SUM_N
+    for name in R.DOMAIN_SUM_INPUTS:
+        values = R.domain_sum_input(name, n)
+        assert values.size == n and not values.flags.writeable
+        with np.errstate(all="ignore"):
+            want = R.sequential_sum(values)
+            assert R.same_bits_nan_class(R.left_to_right(values), want), name
+            for chunk in (4096, 64):
+                got, serial = R.chunked_sum(values, chunk)
+                assert R.same_bits_nan_class(got, want), (name, chunk, got, want)
+                assert 0 <= serial <= n
+                if name == "every_term_a_tie" and chunk == 4096:
+                    assert serial <= n // 4, serial  # records carry the parity: most chunks of ties are applied, not added
+    # each kind is what its name says
+    tiny = 2.0 ** -1022
+    with np.errstate(all="ignore"):
+        s = {name: R.sequential_sum(R.domain_sum_input(name, n)) for name in R.DOMAIN_SUM_INPUTS}
+    assert s["inf_in_the_middle"] == math.inf and math.isnan(s["nan_in_the_middle"]) and math.isnan(s["inf_then_minus_inf"])
+    assert s["finite_overflow"] == math.inf and np.isfinite(R.domain_sum_input("finite_overflow", n)).all()
+    assert 0 < s["subnormal_sum"] < tiny and R.domain_sum_input("subnormal_into_normal", n).max() < tiny < s["subnormal_into_normal"]
+    ties = R.domain_sum_input("every_term_a_tie", n)
+    assert 2.0 ** 52 < s["every_term_a_tie"] < 2.0 ** 53 and np.all(ties[1:] % 1.0 == 0.5)
+    assert s["reaches_2^53_in_a_chunk"] == 2.0 ** 53 and R.sequential_sum(R.domain_sum_input("reaches_2^53_in_a_chunk", 1000)) == 2.0 ** 53 - 1.0
+    assert R.sequential_sum(R.domain_sum_input("chunk_ends_at_2^53-1", 4096)) == 2.0 ** 53 - 1.0 and s["chunk_ends_at_2^53-1"] == 2.0 ** 53
+    zeros = R.domain_sum_input("negative_zeros", n)
+    assert 0.25 < np.count_nonzero(np.signbit(zeros)) / n < 0.35 and s["negative_zeros"] > 0
+    alt = R.domain_sum_input("alternating_positive_sum", n)
+    assert np.all(alt[0::2] > 0) and np.all(alt[1::2] <= 0) and s["alternating_positive_sum"] > 0
+    for name in R.DOMAIN_SUM_INPUTS:  # defined at every size
+        assert [R.domain_sum_input(name, k).size for k in (0, 1, 2)] == [0, 1, 2]
+
+
 # ---- host arithmetic -----------------------------------------------------------------------------------------------------------------------
 def _ulps_from_exact(got: float, exact) -> float:
     return float(abs(mpmath.mpf(got) - exact) / mpmath.mpf(float(np.spacing(abs(float(exact))))))

@@ -107,3 +107,29 @@ def test_image_level_routes(oracle):
     # float-only colour types cannot be u8 images
     with pytest.raises(Exception):
         oracle.convert(rgb, oracle.CS_RGB, oracle.CS_LAB, np.uint8, 3)
+
+
+def test_f32_to_u8_clamps_nan_to_255(oracle):
+    """color.zig:53 `const clamp = std.math.clamp` = @max(lower, @min(val, upper)), and @min / @max return the other operand when one is
+    NaN: clamp(NaN, 0, 1) = 1, so a NaN component becomes the byte 255 (color.zig:117 scalars, :316-318 and :433-436 Rgb / Rgba, :1045 the
+    f32 luminance). Infinities clamp like any value beyond the range, both zeros give 0."""
+    values = np.array([np.nan, -np.nan, np.inf, -np.inf, -0.0, 0.0, 0.5, 1.0, -3e38, 3e38, 1e-45], np.float32)
+    want = np.array([255, 255, 255, 0, 0, 0, 128, 255, 0, 255, 0], np.uint8)
+    spaces = {1: oracle.CS_GRAY, 3: oracle.CS_RGB, 4: oracle.CS_RGBA}
+    for sch in (1, 3, 4):
+        src = values.reshape(1, -1) if sch == 1 else np.repeat(values.reshape(1, -1, 1), sch, axis=2)
+        for dch in (1, 3, 4):
+            got = oracle.convert(np.ascontiguousarray(src), spaces[sch], spaces[dch], np.uint8, dch).reshape(values.size, -1)
+            for i in range(min(dch, 3) if sch > 1 or dch == 1 else 3):
+                assert np.array_equal(got[:, i], want), (sch, dch, i, got[:, i])
+            if dch == 4:  # a missing alpha is opaque; an Rgba source's own alpha goes through the same clamp
+                assert np.array_equal(got[:, 3], want if sch == 4 else np.full(values.size, 255, np.uint8)), (sch, dch)
+    # one NaN field does not touch its neighbours, except through the luminance
+    px = np.array([[[0.25, np.nan, 0.75]]], np.float32)
+    assert oracle.convert(px, oracle.CS_RGB, oracle.CS_RGB, np.uint8, 3).tolist() == [[[64, 255, 191]]]
+    assert oracle.convert(px, oracle.CS_RGB, oracle.CS_GRAY, np.uint8, 1).tolist() == [[255]]
+    # the same conversion ends every other colour type's way to bytes (color.zig:377-379, 497-500): a Lab pixel whose colour maths gives NaN
+    lab = np.array([[[np.nan, 1e30, -np.inf]]], np.float32)
+    with np.errstate(all="ignore"):
+        assert oracle.convert(lab, oracle.CS_LAB, oracle.CS_RGB, np.uint8, 3).tolist() == [[[255, 255, 255]]]
+        assert oracle.convert(lab, oracle.CS_LAB, oracle.CS_RGBA, np.uint8, 4).tolist() == [[[255, 255, 255, 255]]]

@@ -25,7 +25,8 @@ __device__ inline float cs_mod(float x, float y) { // Zig's float @mod
     const float a = fmodf(x, y);
     return x < 0 ? fmodf(a + y, y) : a;
 }
-__device__ inline uint8_t cs_unit_to_u8(float v) { return (uint8_t)(int)roundf(255.0f * cs_clamp(v, 0.0f, 1.0f)); }
+// @round(255 * clamp(v, 0, 1)) into a byte: std.math.clamp = @max(0, @min(v, 1)), where a NaN clamps to 1 and the byte is 255
+__device__ inline uint8_t cs_unit_to_u8(float v) { return (uint8_t)(int)roundf(255.0f * (v != v ? 1.0f : cs_clamp(v, 0.0f, 1.0f))); }
 __device__ inline uint8_t cs_clamp_u8(long long v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
 __device__ inline float cs_gamma_to_linear(float c) { return c > 0.04045f ? dev_powf((c + 0.055f) / 1.055f, 2.4f) : c / 12.92f; } // :1252

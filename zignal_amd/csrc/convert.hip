@@ -27,7 +27,8 @@
 
 namespace zg {
 
-__device__ inline float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+// std.math.clamp(v, 0, 1) = @max(0, @min(v, 1)) and @min / @max return the other operand when one is NaN: NaN clamps to 1 (a byte of 255)
+__device__ inline float clamp01(float v) { return v != v ? 1.0f : (v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v)); }
 __device__ inline uint8_t unit_to_u8(float v) { return (uint8_t)(int)roundf(255.0f * clamp01(v)); }
 __device__ inline uint8_t gray_u8(int r, int g, int b) { // color.zig:1031-1042
     const int v = (13933 * r + 46871 * g + 4732 * b + 32768) >> 16;
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k_convert(DImg src, DImg dst, ConvertArgs
                 else if constexpr (!SF && DF) dv[0] = (float)su[0] / 255.0f;
                 else if constexpr (SF && !DF) {
                     double v = (double)sf[0];
-                    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+                    v = v != v ? 1.0 : (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v)); // NaN clamps to 1, as in clamp01
                     dv[0] = (uint8_t)(int)round(v * 255.0);
                 } else dv[0] = sf[0];
             } else if constexpr (!SF) {
@@ -292,7 +293,9 @@ __global__ __launch_bounds__(256) void k_lab4_to_u8(const uint8_t *__restrict__ 
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             float v = rgb[i];
-            v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); // xyzToRgb's clamp, then the u8 conversion's own (the same function twice)
+            // xyzToRgb's clamp, then the u8 conversion's own (the same function twice): std.math.clamp = @max(0, @min(v, 1)), where a NaN
+            // clamps to 1 (fminf and fmaxf return the other operand); which zero -0.0 becomes does not reach the byte
+            v = fmaxf(0.0f, fminf(v, 1.0f));
             w |= (uint32_t)(uint8_t)(int)roundf(255.0f * v) << (8 * i);
         }
         px[p] = w;

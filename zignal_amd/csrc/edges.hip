@@ -28,7 +28,7 @@ template <int PIX> __device__ inline float sobel_gray(typename Px<PIX>::Vec v) {
         return (float)(y < 0 ? 0 : (y > 255 ? 255 : y));
     } else { // Rgb(f32) / Rgba(f32): clamp(dot, 0, 1) then .as(u8) = @round(255 * clamp) (color.zig:1043-1046, :528-546)
         float y = 0.2126f * v[0] + 0.7152f * v[1] + 0.0722f * v[2];
-        y = y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
+        y = y != y ? 1.0f : (y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y)); // std.math.clamp = @max(0, @min(y, 1)): a NaN clamps to 1
         const float s = 255.0f * y;
         return (float)(int)roundf(s);
     }
@@ -36,9 +36,17 @@ template <int PIX> __device__ inline float sobel_gray(typename Px<PIX>::Vec v) {
 
 // Sobel sums of a 3 x 3 window in the reference's term order (edges.zig:255-262 / image.zig sobel): the zero weights are skipped
 // and the +-1 / +-2 weights folded into additions; the products are exact, so only the sign of a zero can differ.
-__device__ inline void sobel_3x3(const float (&p)[3][3], float &gx, float &gy) {
-    gx = ((((-p[0][0] + p[0][2]) - 2.0f * p[1][0]) + 2.0f * p[1][2]) - p[2][0]) + p[2][2];
-    gy = ((((-p[0][0] - 2.0f * p[0][1]) - p[0][2]) + p[2][0]) + 2.0f * p[2][1]) + p[2][2];
+// ANY_F32: the grey values are an Image(f32)'s own pixels and may be infinite or NaN. convolution.zig:158-169 multiplies every tap, the
+// zero ones too, so an infinity under a zero weight makes the sum NaN (and the byte 255): the three zero products of each sum are kept,
+// in the reference's place. Grey values that came from bytes are finite, and a finite value times zero changes no sum.
+template <bool ANY_F32> __device__ inline void sobel_3x3(const float (&p)[3][3], float &gx, float &gy) {
+    if constexpr (ANY_F32) {
+        gx = (((((((-p[0][0] + p[0][1] * 0.0f) + p[0][2]) - 2.0f * p[1][0]) + p[1][1] * 0.0f) + 2.0f * p[1][2]) - p[2][0]) + p[2][1] * 0.0f) + p[2][2];
+        gy = (((((((-p[0][0] - 2.0f * p[0][1]) - p[0][2]) + p[1][0] * 0.0f) + p[1][1] * 0.0f) + p[1][2] * 0.0f) + p[2][0]) + 2.0f * p[2][1]) + p[2][2];
+    } else {
+        gx = ((((-p[0][0] + p[0][2]) - 2.0f * p[1][0]) + 2.0f * p[1][2]) - p[2][0]) + p[2][2];
+        gy = ((((-p[0][0] - 2.0f * p[0][1]) - p[0][2]) + p[2][0]) + 2.0f * p[2][1]) + p[2][2];
+    }
 }
 
 // Tile 64 x 16 outputs, grey values one pixel around it in LDS (a wave per row, .replicate by clamped coordinates); a thread owns
@@ -74,7 +82,7 @@ __global__ __launch_bounds__(256) void k_sobel(DImg src, DImg dst, int tiles_x, 
     for (int k = 0; k < 4; ++k) {
         const float win[3][3] = {{p[k][0], p[k][1], p[k][2]}, {p[k + 1][0], p[k + 1][1], p[k + 1][2]}, {p[k + 2][0], p[k + 2][1], p[k + 2][2]}};
         float ax, ay;
-        sobel_3x3(win, ax, ay);
+        sobel_3x3<PIX == ZG_PIXEL_F32>(win, ax, ay);
         const float sx = ax * ax, sy = ay * ay;
         const float magnitude = sqrtf(sx + sy);
         const float scaled = magnitude / 4.0f;
@@ -138,7 +146,7 @@ int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t sr
 template <int PIX> __device__ inline float canny_gray(typename Px<PIX>::Vec v) { // as(f32, convertColor(u8, px)), edges.zig:231-240
     if constexpr (PIX == ZG_PIXEL_F32) { // scalar float -> u8 in f64 (color.zig:114-118)
         double d = (double)v[0];
-        d = d < 0.0 ? 0.0 : (d > 1.0 ? 1.0 : d);
+        d = d != d ? 1.0 : (d < 0.0 ? 0.0 : (d > 1.0 ? 1.0 : d)); // std.math.clamp = @max(0, @min(d, 1)): a NaN clamps to 1, the byte is 255
         return (float)(int)round(d * 255.0);
     } else return sobel_gray<PIX>(v);
 }
@@ -219,7 +227,7 @@ __global__ __launch_bounds__(256) void k_canny_nms(const float *blur, uint8_t *s
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float win[3][3] = {{p[k][0], p[k][1], p[k][2]}, {p[k + 1][0], p[k + 1][1], p[k + 1][2]}, {p[k + 2][0], p[k + 2][1], p[k + 2][2]}};
-            sobel_3x3(win, gx[k], gy[k]);
+            sobel_3x3<false>(win, gx[k], gy[k]); // finite: every canny source, Image(f32) included, is clamped into a byte by canny_gray first
             const float sx = gx[k] * gx[k], sy = gy[k] * gy[k];
             m[k] = sqrtf(sx + sy);
             mag[4 * w + k + 1][lane + 1] = m[k];
@@ -238,7 +246,7 @@ __global__ __launch_bounds__(256) void k_canny_nms(const float *blur, uint8_t *s
 #pragma unroll
             for (int i = 0; i < 3; ++i) win[j][i] = b[hr + 1 + j][hc + 1 + i];
         float hx, hy;
-        sobel_3x3(win, hx, hy);
+        sobel_3x3<false>(win, hx, hy); // as above: grey bytes blurred with finite taps
         const float sx = hx * hx, sy = hy * hy;
         mag[hr + 1][hc + 1] = sqrtf(sx + sy);
     }

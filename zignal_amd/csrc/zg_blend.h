@@ -60,19 +60,20 @@ template <int SPIX, int DPIX> __device__ inline typename Px<DPIX>::Vec convert_p
     constexpr bool SF = std::is_same<typename SP::Elem, float>::value, DF = std::is_same<typename DP::Elem, float>::value;
     constexpr int SC = SP::C, DC = DP::C;
     typename DP::Vec d = DP::zero();
-    auto u8_of = [](float v) -> uint8_t { const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); return (uint8_t)(int)roundf(255.0f * c); };
+    // std.math.clamp(v, 0, 1) = @max(0, @min(v, 1)), and @min / @max return the other operand when one is NaN: a NaN clamps to 1 (the byte 255)
+    auto u8_of = [](float v) -> uint8_t { const float c = v != v ? 1.0f : (v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v)); return (uint8_t)(int)roundf(255.0f * c); };
     if constexpr (DC == 1) {
         if constexpr (SC == 1) { // scalar <-> scalar (:113-119)
             if constexpr (SF == DF) d[0] = sv[0];
             else if constexpr (!SF) d[0] = (float)sv[0] / 255.0f;
-            else { double v = (double)sv[0]; v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); d[0] = (uint8_t)(int)round(v * 255.0); }
+            else { double v = (double)sv[0]; v = v != v ? 1.0 : (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v)); d[0] = (uint8_t)(int)round(v * 255.0); }
         } else if constexpr (!SF) { // colour(u8) -> luminance, BT.709 16.16 fixed point
             const int y0 = (13933 * (int)sv[0] + 46871 * (int)sv[1] + 4732 * (int)sv[2] + 32768) >> 16;
             const int y = y0 < 0 ? 0 : (y0 > 255 ? 255 : y0);
             if constexpr (DF) d[0] = (float)y / 255.0f; else d[0] = (uint8_t)y;
         } else {
             float y = 0.2126f * sv[0] + 0.7152f * sv[1] + 0.0722f * sv[2];
-            y = y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y);
+            y = y != y ? 1.0f : (y < 0.0f ? 0.0f : (y > 1.0f ? 1.0f : y)); // rgbToGray's clamp (color.zig:1045): NaN -> 1, for an f32 destination too
             if constexpr (DF) d[0] = y; else d[0] = u8_of(y);
         }
     } else if constexpr (SC == 1) { // scalar -> colour: Gray(Src).as(DestT), replicated, opaque
