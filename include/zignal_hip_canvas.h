@@ -1,5 +1,5 @@
-/* zignal_hip_canvas.h — the Canvas module of libzignal_hip.so: Canvas(T)'s lines, rectangles, circles and polygons (reference
- * src/canvas/Canvas.zig) as one device operation that executes a list of draw commands into an image in place. Included by zignal_hip.h
+/* zignal_hip_canvas.h — the Canvas module of libzignal_hip.so: Canvas(T)'s lines, rectangles, circles, polygons, Bézier curves and
+ * spline polygons (reference src/canvas/Canvas.zig) as one device operation that executes a list of draw commands into an image in place. Included by zignal_hip.h
  * (include that one); zg_image, zg_stream, zg_keypoint and the status codes come from there, zg_hough_line from zignal_hip_hough.h. */
 #ifndef ZIGNAL_HIP_CANVAS_H
 #define ZIGNAL_HIP_CANVAS_H
@@ -20,11 +20,20 @@ extern "C" {
 #define ZG_DRAW_FILL_CIRCLE 4  /* fillCircle(center, radius, color, mode)           p = cx cy radius (:1021-1029) */
 #define ZG_DRAW_POLYGON 5      /* drawPolygon(vertices, color, width, mode)         first_vertex, n_vertices (:579-587) */
 #define ZG_DRAW_FILL_POLYGON 6 /* fillPolygon(vertices, color, mode)                first_vertex, n_vertices (:935-1017) */
+/* Kinds 7-17 are no kinds (16 and 17 are kept for drawArc and fillArc). The curves take their points from the vertex array: */
+#define ZG_DRAW_QUAD_BEZIER 18         /* drawQuadraticBezier(p0, p1, p2, color, width, mode)   n_vertices == 3 (:1221-1245) */
+#define ZG_DRAW_CUBIC_BEZIER 19        /* drawCubicBezier(p0, p1, p2, p3, color, width, mode)   n_vertices == 4 (:1249-1275) */
+#define ZG_DRAW_SPLINE_POLYGON 20      /* drawSplinePolygon(vertices, color, width, tension, mode)  vertex range, p[0] = tension (:1280-1291) */
+#define ZG_DRAW_FILL_SPLINE_POLYGON 21 /* fillSplinePolygon(vertices, color, tension, mode)         vertex range, p[0] = tension (:1296-1355) */
 
 #define ZG_DRAW_FAST 0 /* DrawMode.fast: hard edges */
 #define ZG_DRAW_SOFT 1 /* DrawMode.soft: antialiased edges, Rgba alpha honoured */
 
-#define ZG_CANVAS_MAX_VERTICES 64u  /* vertices of one polygon: the reference's stack buffer (Canvas.zig:52) */
+#define ZG_CANVAS_MAX_VERTICES 64u  /* vertices of one polygon or spline polygon: the reference's stack buffer (Canvas.zig:52) */
+/* points of the polygon a filled spline polygon is tessellated into: the sum over its edges of clamp(trunc(length / 3), 4, 50), length
+ * being the reference's estimate for the edge's cubic (:1318-1328). The reference spills to the heap past 400; this is the library's bound.
+ * (It also holds the 402 points a soft arc outline would need, should arcs follow.) */
+#define ZG_CANVAS_MAX_CURVE_POINTS 512u
 #define ZG_CANVAS_MAX_COORD 65536.0f /* every float parameter and vertex coordinate: finite and |v| <= this */
 #define ZG_CANVAS_MAX_WIDTH 65536u  /* width */
 #define ZG_CANVAS_MAX_SIZE 32768u   /* rows and cols of the image drawn into */
@@ -34,14 +43,15 @@ extern "C" {
  * through setPixel, which converts the (faded) colour to the pixel type before assignPixel sees it: an Rgba(u8) image is composited
  * into with Rgba.blend(.normal) when a != 255; a u8 or Rgb(u8) image is stored to with convertColor(T, color) whatever the alpha —
  * soft edges and translucent colours overwrite there, exactly as in the reference. width is ignored by the fills; width == 0, radius <= 0 and a filled polygon of
- * fewer than 3 vertices draw nothing, as in the reference (drawPolygon draws its edges whatever their number). 40 bytes, no padding. */
+ * fewer than 3 vertices draw nothing, as in the reference (drawPolygon draws its edges whatever their number); so do a Bézier of width 0
+ * and a spline polygon of width 0 (the outline) or of fewer than 3 vertices. 40 bytes, no padding. */
 typedef struct zg_draw_cmd {
     int32_t kind;  /* ZG_DRAW_* */
     int32_t mode;  /* ZG_DRAW_FAST | ZG_DRAW_SOFT */
     uint32_t width;
     uint8_t color[4]; /* r g b a */
     float p[4];
-    uint32_t first_vertex, n_vertices; /* polygons: vertices[first_vertex .. first_vertex + n_vertices) of the call's vertex array */
+    uint32_t first_vertex, n_vertices; /* polygons and curves: vertices[first_vertex .. first_vertex + n_vertices) of the call's vertex array */
 } zg_draw_cmd;
 /* sizeof(zg_draw_cmd) as the library was built: a binding that declares the struct itself compares and refuses to go on when they
  * differ (the zg_sizeof_step rule). */
@@ -59,16 +69,20 @@ ZG_API uint32_t zg_canvas_tile(void);
  * executed. vertices: n_vertices float pairs (x, y) on the device, NULL when n_vertices is 0.
  * A command outside the contract — a kind or mode that is none of the above, a float parameter or vertex that is not finite or
  * exceeds ZG_CANVAS_MAX_COORD in magnitude, a width above ZG_CANVAS_MAX_WIDTH, more than ZG_CANVAS_MAX_VERTICES vertices or a vertex
- * range outside the array (the reference would trap in its @trunc casts or index past a slice) — is skipped on the device.
+ * range outside the array (the reference would trap in its @trunc casts or index past a slice), a Bézier whose n_vertices is not its
+ * number of control points, a spline polygon's tension that is not finite, a filled spline polygon of more than
+ * ZG_CANVAS_MAX_CURVE_POINTS points — is skipped on the device.
  * n above ZG_CANVAS_MAX_COMMANDS: ZG_ERR_UNSUPPORTED. Cost: every tile tests every command's box; a width-1 soft line and a width-1 fast
- * circle are re-walked from their start by the tiles they cross, so their time grows with their length as well as with the tiles.
+ * circle are re-walked from their start by the tiles they cross, so their time grows with their length as well as with the tiles; a
+ * Bézier is its 3 to 200 lines, each tested against the tile before it is drawn.
  * Asynchronous on `stream`, two launches, 8 bytes of scratch per command, no host synchronisation, copy or upload, recordable into a
  * graph from a process's first call. In a process without a device the call answers its argument errors, then ZG_ERR_HIP. */
 ZG_API int zg_canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices,
                           uint32_t n_vertices, zg_stream stream);
 
 /* Host pointers (img->data, cmds, vertices), synchronous. Here a command outside the contract is refused before anything is drawn:
- * ZG_ERR_UNSUPPORTED for a polygon of more than ZG_CANVAS_MAX_VERTICES vertices, ZG_ERR_INVALID_ARGUMENT for everything else. */
+ * ZG_ERR_UNSUPPORTED for a polygon or spline polygon of more than ZG_CANVAS_MAX_VERTICES vertices and for a filled spline polygon of
+ * more than ZG_CANVAS_MAX_CURVE_POINTS points, ZG_ERR_INVALID_ARGUMENT for everything else. */
 ZG_API int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, uint32_t n_vertices);
 
 /* Device-side builders, one lane per entry, so that a detector's list becomes a command list without the host seeing either.

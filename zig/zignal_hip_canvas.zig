@@ -1,4 +1,4 @@
-//! zignal_hip_canvas.zig — the Canvas module of the shim: Canvas(T)'s lines, rectangles, circles and polygons (reference
+//! zignal_hip_canvas.zig — the Canvas module of the shim: Canvas(T)'s lines, rectangles, circles, polygons, Bézier curves and spline polygons (reference
 //! src/canvas/Canvas.zig) through libzignal_hip.so's zg_canvas_* entry points (include/zignal_hip_canvas.h). Like the other files of
 //! the shim it has not been compiled where the library is built (no Zig toolchain).
 const std = @import("std");
@@ -19,7 +19,9 @@ comptime {
     std.debug.assert(@sizeOf(c.ZgDrawCmd) == 40);
 }
 
-pub const Kind = enum(i32) { line = 0, rectangle = 1, fill_rectangle = 2, circle = 3, fill_circle = 4, polygon = 5, fill_polygon = 6 };
+pub const Kind = enum(i32) { line = 0, rectangle = 1, fill_rectangle = 2, circle = 3, fill_circle = 4, polygon = 5, fill_polygon = 6, quad_bezier = 18, cubic_bezier = 19, spline_polygon = 20, fill_spline_polygon = 21 };
+/// ZG_CANVAS_MAX_CURVE_POINTS: the points a filled spline polygon may tessellate into
+pub const max_curve_points: u32 = 512;
 pub const DrawMode = zignal.DrawMode;
 const Rgba = zignal.Rgba(u8);
 const Point = zignal.Point(2, f32);
@@ -59,9 +61,12 @@ pub fn Canvas(comptime T: type) type {
             try self.cmds.append(self.allocator, .{ .kind = @intFromEnum(kind), .mode = if (mode == .soft) 1 else 0, .width = width, .color = .{ color.r, color.g, color.b, color.a }, .p = p });
         }
         fn addPolygon(self: *Self, kind: Kind, polygon: []const Point, mode: DrawMode, width: u32, color: Rgba) !void {
+            try self.addPoints(kind, polygon, mode, width, color, 0);
+        }
+        fn addPoints(self: *Self, kind: Kind, polygon: []const Point, mode: DrawMode, width: u32, color: Rgba, p0: f32) !void {
             const first: u32 = @intCast(self.vertices.items.len / 2);
             for (polygon) |pt| try self.vertices.appendSlice(self.allocator, &.{ pt.x(), pt.y() });
-            try self.add(kind, mode, width, color, .{ 0, 0, 0, 0 });
+            try self.add(kind, mode, width, color, .{ p0, 0, 0, 0 });
             self.cmds.items[self.cmds.items.len - 1].first_vertex = first;
             self.cmds.items[self.cmds.items.len - 1].n_vertices = @intCast(polygon.len);
         }
@@ -85,6 +90,19 @@ pub fn Canvas(comptime T: type) type {
         }
         pub fn fillPolygon(self: *Self, polygon: []const Point, color: Rgba, mode: DrawMode) !void {
             try self.addPolygon(.fill_polygon, polygon, mode, 1, color);
+        }
+        pub fn drawQuadraticBezier(self: *Self, p0: Point, p1: Point, p2: Point, color: Rgba, width: u32, mode: DrawMode) !void {
+            try self.addPoints(.quad_bezier, &.{ p0, p1, p2 }, mode, width, color, 0);
+        }
+        pub fn drawCubicBezier(self: *Self, p0: Point, p1: Point, p2: Point, p3: Point, color: Rgba, width: u32, mode: DrawMode) !void {
+            try self.addPoints(.cubic_bezier, &.{ p0, p1, p2, p3 }, mode, width, color, 0);
+        }
+        pub fn drawSplinePolygon(self: *Self, polygon: []const Point, color: Rgba, width: u32, tension: f32, mode: DrawMode) !void {
+            try self.addPoints(.spline_polygon, polygon, mode, width, color, tension);
+        }
+        /// At most max_curve_points points once tessellated: past that flush() fails and draws nothing.
+        pub fn fillSplinePolygon(self: *Self, polygon: []const Point, color: Rgba, tension: f32, mode: DrawMode) !void {
+            try self.addPoints(.fill_spline_polygon, polygon, mode, 1, color, tension);
         }
         pub fn flush(self: *Self) !void {
             defer self.cmds.clearRetainingCapacity();

@@ -142,8 +142,10 @@ class ZgDrawCmd(C.Structure):
 
 
 DRAW_LINE, DRAW_RECT, DRAW_FILL_RECT, DRAW_CIRCLE, DRAW_FILL_CIRCLE, DRAW_POLYGON, DRAW_FILL_POLYGON = range(7)
+DRAW_QUAD_BEZIER, DRAW_CUBIC_BEZIER, DRAW_SPLINE_POLYGON, DRAW_FILL_SPLINE_POLYGON = range(18, 22)  # 7-17 are no kinds
 DRAW_FAST, DRAW_SOFT = range(2)
 CANVAS_MAX_VERTICES, CANVAS_MAX_COORD, CANVAS_MAX_WIDTH, CANVAS_MAX_SIZE, CANVAS_MAX_COMMANDS = 64, 65536.0, 65536, 32768, 1 << 24  # ZG_CANVAS_MAX_*
+CANVAS_MAX_CURVE_POINTS = 512
 
 
 class ZgMetricResult(C.Structure):

@@ -1,5 +1,5 @@
 """Canvas(T) (reference src/canvas/Canvas.zig) over the zg_canvas_* entry points (include/zignal_hip_canvas.h): lines, rectangles,
-circles and polygons drawn into a u8, Rgb(u8) or Rgba(u8) image in place, as one device operation over a command list. The result
+circles, polygons, Bézier curves and spline polygons drawn into a u8, Rgb(u8) or Rgba(u8) image in place, as one device operation over a command list. The result
 equals the reference making the same calls one after another, byte for byte.
 
     cv = zg.Canvas(image)                       # a device (or host) zg.Image or the tensor / array under it
@@ -48,8 +48,8 @@ def canvas_tile() -> int:
 
 
 def pack_commands(commands):
-    """A list of command dicts — kind (zignal_amd._lib.DRAW_*), mode, width, color and p (the float parameters) or pts (polygon
-    vertices) — as (a DRAW_CMD_DTYPE array, an (n_vertices, 2) float32 array): the host form of zg_canvas_draw's two lists."""
+    """A list of command dicts — kind (zignal_amd._lib.DRAW_*), mode, width, color and p (the float parameters), pts (polygon vertices
+    or a curve's points) or both (a spline polygon: p = [tension]) — as (a DRAW_CMD_DTYPE array, an (n_vertices, 2) float32 array): the host form of zg_canvas_draw's two lists."""
     cmds = np.zeros(len(commands), DRAW_CMD_DTYPE)
     vertices = []
     for i, c in enumerate(commands):
@@ -58,7 +58,7 @@ def pack_commands(commands):
         if "pts" in c:
             cmds[i]["first_vertex"], cmds[i]["n_vertices"] = len(vertices), len(c["pts"])
             vertices += [(float(x), float(y)) for x, y in c["pts"]]
-        else:
+        if "p" in c or "pts" not in c:  # a command with neither is an error (KeyError), as it always was
             p = [float(v) for v in c["p"]]
             cmds[i]["p"] = p + [0.0] * (4 - len(p))
     return cmds, np.asarray(vertices, np.float32).reshape(-1, 2)
@@ -66,7 +66,8 @@ def pack_commands(commands):
 
 def draw_host(image, cmds: np.ndarray, vertices=None) -> None:
     """zg_canvas_draw_host: host pixels (a numpy array or a host zg.Image), a DRAW_CMD_DTYPE array and float32 vertex pairs. Synchronous;
-    a command outside the contract raises InvalidArgument (a polygon of more than 64 vertices: ZignalError, unsupported)."""
+    a command outside the contract raises InvalidArgument (a polygon of more than 64 vertices or a filled spline polygon of more than
+    CANVAS_MAX_CURVE_POINTS points: ZignalError, unsupported)."""
     img = image if isinstance(image, Image) else Image(image)
     cmds = np.ascontiguousarray(cmds, DRAW_CMD_DTYPE)
     v = np.ascontiguousarray(np.zeros((0, 2), np.float32) if vertices is None else vertices, np.float32).reshape(-1, 2)
@@ -144,7 +145,7 @@ class Canvas:
         c = {"kind": kind, "mode": _mode(mode), "width": int(width), "color": _color(color)}
         if pts is not None:
             c["pts"] = [(float(x), float(y)) for x, y in pts]
-        else:
+        if p is not None or pts is None:
             c["p"] = [float(v) for v in p]
         self.commands.append(c)
         return self
@@ -170,6 +171,20 @@ class Canvas:
 
     def fill_polygon(self, points, color, mode="fast"):
         return self._add(L.DRAW_FILL_POLYGON, color, 1, mode, pts=points)
+
+    def draw_quadratic_bezier(self, p0, p1, p2, color, width: int = 1, mode="fast"):
+        return self._add(L.DRAW_QUAD_BEZIER, color, width, mode, pts=(p0, p1, p2))
+
+    def draw_cubic_bezier(self, p0, p1, p2, p3, color, width: int = 1, mode="fast"):
+        return self._add(L.DRAW_CUBIC_BEZIER, color, width, mode, pts=(p0, p1, p2, p3))
+
+    def draw_spline_polygon(self, points, color, width: int = 1, tension: float = 0.5, mode="fast"):
+        """The polygon's edges as cubic Béziers through its vertices; tension 0 (sharp corners) to 1 (smoothest), clamped."""
+        return self._add(L.DRAW_SPLINE_POLYGON, color, width, mode, p=(tension,), pts=points)
+
+    def fill_spline_polygon(self, points, color, tension: float = 0.5, mode="fast"):
+        """At most CANVAS_MAX_CURVE_POINTS points once tessellated (3 pixels a segment, 4 to 50 points an edge)."""
+        return self._add(L.DRAW_FILL_SPLINE_POLYGON, color, 1, mode, p=(tension,), pts=points)
 
     def flush(self, stream=None) -> None:
         """Draw the list and empty it. Device image: the two lists are uploaded (one synchronous copy each) and zg_canvas_draw runs on

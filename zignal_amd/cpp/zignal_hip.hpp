@@ -967,7 +967,8 @@ inline void HoughTransform::computeInto(const DeviceImage<uint8_t> &edges, const
 // ---- canvas: Canvas(T) (src/canvas/Canvas.zig) ----
 enum class DrawMode { fast = ZG_DRAW_FAST, soft = ZG_DRAW_SOFT };                         // Canvas.zig:19-24
 struct Point2 { float x, y; };
-// Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods append to a command list, flush()
+// Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods (lines, rectangles, circles,
+// polygons, Bézier curves, spline polygons) append to a command list, flush()
 // executes it into the image in list order (zg_canvas_draw_host for host pixels; for device pixels the two lists are uploaded and
 // zg_canvas_draw runs on the image's stream) and empties it. The result equals the reference making the same calls, byte for byte.
 template <typename T, template <class> class Img = Image> class Canvas {
@@ -997,6 +998,20 @@ template <typename T, template <class> class Img = Image> class Canvas {
     }
     Canvas &fillPolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) {
         return addPolygon(ZG_DRAW_FILL_POLYGON, polygon, mode, 1, color);
+    }
+    Canvas &drawQuadraticBezier(Point2 p0, Point2 p1, Point2 p2, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_QUAD_BEZIER, {p0, p1, p2}, mode, width, color);
+    }
+    Canvas &drawCubicBezier(Point2 p0, Point2 p1, Point2 p2, Point2 p3, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_CUBIC_BEZIER, {p0, p1, p2, p3}, mode, width, color);
+    }
+    // tension: 0 (sharp corners) to 1 (smoothest), clamped as in the reference
+    Canvas &drawSplinePolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, uint32_t width, float tension, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_SPLINE_POLYGON, polygon, mode, width, color, tension);
+    }
+    // at most ZG_CANVAS_MAX_CURVE_POINTS points once tessellated
+    Canvas &fillSplinePolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, float tension, DrawMode mode = DrawMode::fast) {
+        return addPolygon(ZG_DRAW_FILL_SPLINE_POLYGON, polygon, mode, 1, color, tension);
     }
     const std::vector<zg_draw_cmd> &commands() const { return cmds_; }
     void flush() {
@@ -1035,8 +1050,8 @@ template <typename T, template <class> class Img = Image> class Canvas {
         cmds_.push_back(cmd);
         return *this;
     }
-    Canvas &addPolygon(int kind, const std::vector<Point2> &polygon, DrawMode mode, uint32_t width, Rgba<uint8_t> color) {
-        add(kind, mode, width, color, 0, 0, 0, 0);
+    Canvas &addPolygon(int kind, const std::vector<Point2> &polygon, DrawMode mode, uint32_t width, Rgba<uint8_t> color, float p0 = 0.0f) {
+        add(kind, mode, width, color, p0, 0, 0, 0);
         cmds_.back().first_vertex = (uint32_t)(vertices_.size() / 2);
         cmds_.back().n_vertices = (uint32_t)polygon.size();
         for (const Point2 &p : polygon) { vertices_.push_back(p.x); vertices_.push_back(p.y); }

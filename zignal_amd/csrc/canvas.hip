@@ -3,6 +3,8 @@
 //                             (fillPolygon of four corners, two fillCircle(.fast)), the thick soft line by distance and its axis-aligned form
 //   drawPolygon, drawRectangle :579-601 (drawLine per edge), fillRectangle :608-632, fillPolygon :935-1017
 //   drawCircle, fillCircle :636-644, :752-876, :1021-1084 (drawBresenhamCircle, renderRing, fillCircleFast's spans)
+//   drawQuadraticBezier, drawCubicBezier :1221-1275, :1360-1455 (tessellated by the lanes into LDS, then drawLine per segment in order)
+//   drawSplinePolygon, fillSplinePolygon :1280-1355, :1460-1472 (a cubic per edge; the fill is one fillPolygon over all edges' points)
 // composited with Rgba.blend(.normal) and convertColor exactly as Image.insert does (zg_blend.h).
 //
 // The reference's result at a pixel is a fold, in call order, over every write any call makes to that pixel, and blending writes do not
@@ -33,19 +35,71 @@ namespace zg {
 
 constexpr int CV_TILE = 16;
 constexpr int CV_CHUNK = 1024; // commands a workgroup tests against its tile between two barriers
+constexpr int CV_POINTS = ZG_CANVAS_MAX_CURVE_POINTS; // vertices of the largest polygon poly_fill is handed
+constexpr int CV_CURVE_BASE = 8; // a Bézier's points sit in s_vx / s_vy from here: below it a thick fast line keeps its four corners
 constexpr float CV_TILE_REACH = 11.4f; // from a tile's centre (7.5, 7.5) to its farthest pixel centre, rounded up
 using Rgba8 = typename Px<ZG_PIXEL_RGBA_U8>::Vec;
 
-// 0: inside the contract; 1: outside it; 2: a polygon of more than ZG_CANVAS_MAX_VERTICES vertices
+// The reference's tessellation constants (:36-48): segment counts are max(min, min(max, trunc(estimated length / pixels per segment)))
+constexpr int CV_BEZIER_MAX_SEGMENTS = 200, CV_SPLINE_MAX_SEGMENTS = 50, CV_SPLINE_MIN_SEGMENTS = 4, CV_QUADRATIC_MIN_SEGMENTS = 3;
+constexpr float CV_PPS_SOFT = 1.5f, CV_PPS_FAST = 3.0f, CV_PPS_QUADRATIC = 2.0f;
+
+struct CvPoint { float x, y; };
+__host__ __device__ __forceinline__ float cv_distance(CvPoint a, CvPoint b) { // Point.distance: sub, dot with itself, @sqrt
+    const float dx = a.x - b.x, dy = a.y - b.y;
+    return sqrtf(dx * dx + dy * dy);
+}
+__host__ __device__ __forceinline__ int cv_segments(float estimated_length, float pixels_per_segment, int min_segments, int max_segments) { // :1416
+    const float q = truncf(estimated_length / pixels_per_segment); // finite and below 2^21 for coordinates inside the contract
+    const int s = q < (float)max_segments ? (int)q : max_segments;
+    return s > min_segments ? s : min_segments;
+}
+__host__ __device__ __forceinline__ float cv_cubic_length(CvPoint p0, CvPoint p1, CvPoint p2, CvPoint p3) { // estimateCubicBezierLength (:1398-1403)
+    const float chord = cv_distance(p0, p3);
+    const float control_net = cv_distance(p0, p1) + cv_distance(p1, p2) + cv_distance(p2, p3);
+    return (chord + control_net) / 2.0f;
+}
+// calculateSmoothControlPoints (:1460-1472) for the edge from vertex i to vertex i + 1 of the spline polygon v[0 .. n)
+__host__ __device__ __forceinline__ void cv_spline_edge(const float *v, uint32_t n, uint32_t i, float tension, CvPoint &p0, CvPoint &cp1, CvPoint &cp2, CvPoint &p1) {
+    const uint32_t i1 = (i + 1) % n, i2 = (i + 2) % n;
+    const float tension_factor = 1.0f - fmaxf(0.0f, fminf(tension, 1.0f));
+    p0 = {v[2 * i], v[2 * i + 1]};
+    p1 = {v[2 * i1], v[2 * i1 + 1]};
+    const CvPoint p2 = {v[2 * i2], v[2 * i2 + 1]};
+    cp1 = {p0.x + (p1.x - p0.x) * tension_factor, p0.y + (p1.y - p0.y) * tension_factor};
+    cp2 = {p1.x - (p2.x - p1.x) * tension_factor, p1.y - (p2.y - p1.y) * tension_factor};
+}
+// fillSplinePolygon's total_points (:1318-1328)
+__host__ __device__ __forceinline__ uint32_t cv_spline_fill_points(const float *v, uint32_t n, float tension) {
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        CvPoint p0, cp1, cp2, p1;
+        cv_spline_edge(v, n, i, tension, p0, cp1, cp2, p1);
+        total += (uint32_t)cv_segments(cv_cubic_length(p0, cp1, cp2, p1), CV_PPS_FAST, CV_SPLINE_MIN_SEGMENTS, CV_SPLINE_MAX_SEGMENTS);
+    }
+    return total;
+}
+
+// 0: inside the contract; 1: outside it; 2: a polygon or spline polygon of more than ZG_CANVAS_MAX_VERTICES vertices; 3: a filled spline
+// polygon of more than ZG_CANVAS_MAX_CURVE_POINTS points
 __host__ __device__ inline bool cv_coord_ok(float v) { return fabsf(v) <= ZG_CANVAS_MAX_COORD; } // false for NaN and the infinities
+__host__ __device__ inline bool cv_takes_vertices(int kind) { return kind == ZG_DRAW_POLYGON || kind == ZG_DRAW_FILL_POLYGON || kind >= ZG_DRAW_QUAD_BEZIER; }
 __host__ __device__ inline int cv_check(const zg_draw_cmd &c, const float *vertices, uint32_t n_vertices) {
-    if (c.kind < ZG_DRAW_LINE || c.kind > ZG_DRAW_FILL_POLYGON || (c.mode != ZG_DRAW_FAST && c.mode != ZG_DRAW_SOFT)) return 1;
+    const bool known = (c.kind >= ZG_DRAW_LINE && c.kind <= ZG_DRAW_FILL_POLYGON) || (c.kind >= ZG_DRAW_QUAD_BEZIER && c.kind <= ZG_DRAW_FILL_SPLINE_POLYGON);
+    if (!known || (c.mode != ZG_DRAW_FAST && c.mode != ZG_DRAW_SOFT)) return 1;
     if (c.width > ZG_CANVAS_MAX_WIDTH) return 1;
-    if (c.kind == ZG_DRAW_POLYGON || c.kind == ZG_DRAW_FILL_POLYGON) {
-        if (c.n_vertices > ZG_CANVAS_MAX_VERTICES) return 2;
+    if (cv_takes_vertices(c.kind)) {
+        if (c.kind == ZG_DRAW_QUAD_BEZIER || c.kind == ZG_DRAW_CUBIC_BEZIER) {
+            if (c.n_vertices != (c.kind == ZG_DRAW_QUAD_BEZIER ? 3u : 4u)) return 1;
+        } else if (c.n_vertices > ZG_CANVAS_MAX_VERTICES) return 2;
         if (c.first_vertex > n_vertices || c.n_vertices > n_vertices - c.first_vertex) return 1;
         for (uint32_t i = 0; i < c.n_vertices; ++i)
             if (!cv_coord_ok(vertices[2 * (size_t)(c.first_vertex + i)]) || !cv_coord_ok(vertices[2 * (size_t)(c.first_vertex + i) + 1])) return 1;
+        if (c.kind == ZG_DRAW_SPLINE_POLYGON || c.kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
+            if (!cv_coord_ok(c.p[0])) return 1; // the tension
+            if (c.kind == ZG_DRAW_FILL_SPLINE_POLYGON && c.n_vertices >= 3 &&
+                cv_spline_fill_points(vertices + 2 * (size_t)c.first_vertex, c.n_vertices, c.p[0]) > ZG_CANVAS_MAX_CURVE_POINTS) return 3;
+        }
         return 0;
     }
     const int np = (c.kind == ZG_DRAW_CIRCLE || c.kind == ZG_DRAW_FILL_CIRCLE) ? 3 : 4;
@@ -97,15 +151,24 @@ __global__ __launch_bounds__(256) void k_canvas_prep(const zg_draw_cmd *cmds, ui
             pad = (c.kind == ZG_DRAW_CIRCLE ? 0.5f * (float)c.width : 0.0f) + 3.0f;
             draws = c.p[2] > 0 && (c.kind == ZG_DRAW_FILL_CIRCLE || c.width != 0);
             break;
-        default: { // the polygons
-            draws = c.kind == ZG_DRAW_POLYGON ? (c.width != 0 && c.n_vertices != 0) : c.n_vertices >= 3;
+        default: { // the polygons and the curves: a Bézier stays inside the hull of its control points
+            const bool outline = c.kind != ZG_DRAW_FILL_POLYGON && c.kind != ZG_DRAW_FILL_SPLINE_POLYGON;
+            const bool spline = c.kind == ZG_DRAW_SPLINE_POLYGON || c.kind == ZG_DRAW_FILL_SPLINE_POLYGON;
+            draws = outline ? (c.width != 0 && c.n_vertices >= (spline ? 3u : 1u)) : c.n_vertices >= 3;
             if (draws) {
                 const float *v = vertices + 2 * (size_t)c.first_vertex;
                 x0 = x1 = v[0]; y0 = y1 = v[1];
                 for (uint32_t k = 1; k < c.n_vertices; ++k) {
                     x0 = fminf(x0, v[2 * k]); x1 = fmaxf(x1, v[2 * k]); y0 = fminf(y0, v[2 * k + 1]); y1 = fmaxf(y1, v[2 * k + 1]);
                 }
-                pad = c.kind == ZG_DRAW_POLYGON ? cv_line_pad(x0, y0, x1, y1, c.width, c.mode) : 2.0f;
+                if (spline) { // cp1 lies between two vertices; cp2 = p1 - (p2 - p1) * tf with tf in [0, 1] lies between p1 and 2 p1 - p2
+                    for (uint32_t k = 0; k < c.n_vertices; ++k) {
+                        const uint32_t k1 = (k + 1) % c.n_vertices, k2 = (k + 2) % c.n_vertices;
+                        const float mx = v[2 * k1] - (v[2 * k2] - v[2 * k1]), my = v[2 * k1 + 1] - (v[2 * k2 + 1] - v[2 * k1 + 1]);
+                        x0 = fminf(x0, mx); x1 = fmaxf(x1, mx); y0 = fminf(y0, my); y1 = fmaxf(y1, my);
+                    }
+                }
+                pad = outline ? cv_line_pad(x0, y0, x1, y1, c.width, c.mode) : 2.0f;
             }
         }
         }
@@ -152,21 +215,18 @@ __device__ inline Rgba8 cv_fade(Rgba8 c, float alpha) { // Rgba(u8).fade (color.
 }
 __device__ inline float cv_fpart(float x) { return x - floorf(x); }
 __device__ inline float cv_rfpart(float x) { return 1.0f - cv_fpart(x); }
-
-// One lane's view of the canvas: its pixel in registers and the reference's drawing routines, each reduced to "does this call write my
-// pixel, and with what". Routines that use LDS or a barrier (poly_fill, disc_fast, the axis-aligned line and their callers) are entered by all 256 lanes of the workgroup
-// together: every branch around them depends on the command and the tile only.
 template <int PIX> struct Cv {
     using P = Px<PIX>;
     typename P::Vec px;
     bool dirty, inside;
     int col, row, tx0, ty0, tid;
     float fx, fy, fcols, frows;
-    float *s_vx, *s_vy, *s_ix; // polygon vertices [64], [64]; sorted intersections [16][64]
+    float *s_vx, *s_vy, *s_ix; // polygon vertices [CV_POINTS], [CV_POINTS]; sorted intersections [16][CV_POINTS]
     float *s_row;              // what a disc or an axis-aligned line computes once per tile row or column [16][3]
     int *s_icnt;               // intersections per tile row [16]
+    unsigned long long *s_near; // a curve's segments that can reach the tile, one bit each [4]
 
-    __device__ void solid(Rgba8 c) { // dest.* = convertColor(T, color)
+    __device__ __forceinline__ void solid(Rgba8 c) { // dest.* = convertColor(T, color)
         if (!inside) return;
         px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
         dirty = true;
@@ -174,7 +234,7 @@ template <int PIX> struct Cv {
     // setPixel with an Rgba colour (:504-514): it hands assignPixel (image.zig:67-94) convertColor(T, color), so only an Rgba destination still
     // has an Rgba sample to blend (when a != 255). On u8 and Rgb the converted sample has lost its alpha and is stored whatever the alpha was,
     // a faded alpha of 0 included.
-    __device__ void pixel(Rgba8 c) {
+    __device__ __forceinline__ void pixel(Rgba8 c) {
         if (!inside) return;
         if constexpr (PIX == ZG_PIXEL_RGBA_U8) {
             if (c[3] != 255) blend_u8(px, c, 1); else px = c;
@@ -183,27 +243,27 @@ template <int PIX> struct Cv {
         }
         dirty = true;
     }
-    __device__ void point(float x, float y, Rgba8 c) { // setPoint (:518-523)
+    __device__ __forceinline__ void point(float x, float y, Rgba8 c) { // setPoint (:518-523)
         if (floorf(x) == fx && floorf(y) == fy) pixel(c);
     }
-    __device__ void span(float x1, float x2, float y, Rgba8 c) { // setHorizontalSpan (:129-145)
+    __device__ __forceinline__ void span(float x1, float x2, float y, Rgba8 c) { // setHorizontalSpan (:129-145)
         if (y < 0 || y >= frows) return;
         if (x2 < 0 || x1 >= fcols) return;
         const int r = (int)y, start = (int)fmaxf(0.0f, floorf(x1)), end = (int)fminf(fcols - 1, ceilf(x2));
         if (r == row && col >= start && col <= end) solid(c);
     }
     // clampRectToImage (:62-79)
-    __device__ bool clamp_rect(float l, float t, float r, float b, int &left, int &top, int &right, int &bottom) const {
+    __device__ __forceinline__ bool clamp_rect(float l, float t, float r, float b, int &left, int &top, int &right, int &bottom) const {
         left = (int)cv_clamp(l, 0.0f, fcols); top = (int)cv_clamp(t, 0.0f, frows);
         right = (int)cv_clamp(r, 0.0f, fcols); bottom = (int)cv_clamp(b, 0.0f, frows);
         return !(left >= right || top >= bottom);
     }
-    __device__ float tile_distance(float cx, float cy) const { // from the tile's centre to (cx, cy)
+    __device__ __forceinline__ float tile_distance(float cx, float cy) const { // from the tile's centre to (cx, cy)
         const float dx = (float)tx0 + 7.5f - cx, dy = (float)ty0 + 7.5f - cy;
         return sqrtf(dx * dx + dy * dy);
     }
 
-    __device__ void fill_rect(float l, float t, float r, float b, Rgba8 color, int mode) { // :608-632
+    __device__ __forceinline__ void fill_rect(float l, float t, float r, float b, Rgba8 color, int mode) { // :608-632
         int left, top, right, bottom;
         if (!clamp_rect(l, t, r, b, left, top, right, bottom)) return;
         if (col < left || col >= right || row < top || row >= bottom) return;
@@ -211,7 +271,7 @@ template <int PIX> struct Cv {
     }
 
     // renderRing over the full circle (:794-822) with ringBoundingBox and ringCoverage (:754-786)
-    __device__ void ring(float cx, float cy, float inner, float outer, Rgba8 color, int mode) {
+    __device__ __forceinline__ void ring(float cx, float cy, float inner, float outer, Rgba8 color, int mode) {
         const float dc = tile_distance(cx, cy);
         if (dc - CV_TILE_REACH > outer + 3.0f || (inner > 0 && dc + CV_TILE_REACH < inner - 3.0f)) return; // the tile misses the ring
         const int left = (int)roundf(cv_clamp(cx - outer - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - outer - 1, 0.0f, frows));
@@ -240,7 +300,7 @@ template <int PIX> struct Cv {
     // drawBresenhamCircle over the full circle (:826-860): f32 state that only ever holds integers. The step (x, y) that can reach this
     // pixel is fixed by the pixel (x = the larger, y = the smaller of its |offsets|); the lane walks to it, then makes the step's eight
     // setPoint calls in their order, so a pixel that two of the offsets name (y == 0, x == y) is written twice.
-    __device__ void circle_bresenham(float center_x, float center_y, float radius, Rgba8 color) {
+    __device__ __forceinline__ void circle_bresenham(float center_x, float center_y, float radius, Rgba8 color) {
         const float cx = roundf(center_x), cy = roundf(center_y), r = roundf(radius);
         const float dc = tile_distance(cx, cy);
         if (dc - CV_TILE_REACH > r + 2.0f || dc + CV_TILE_REACH < r - 2.0f) return;
@@ -269,7 +329,7 @@ template <int PIX> struct Cv {
     // a binade and rounds only when it crosses a power of two, so the lane replays the walk a binade at a time up to its own row
     // (tests/canvas_ref.py: disc_row_y, held to the literal walk): y is the walk's value in this row, if it has one. The row's y and span
     // ends are the same for the whole row: lanes 0-15 compute them once per (disc, tile row) into LDS. Entered by all lanes together.
-    __device__ void disc_fast(float cx, float cy, float radius, Rgba8 color) {
+    __device__ __forceinline__ void disc_fast(float cx, float cy, float radius, Rgba8 color) {
         if (tile_distance(cx, cy) - CV_TILE_REACH > radius + 3.0f) return;
         if (tid < CV_TILE) {
             const int r = ty0 + tid;
@@ -304,14 +364,14 @@ template <int PIX> struct Cv {
 
     // fillPolygon (:935-1017) of the n >= 3 vertices in s_vx / s_vy. Lanes 0-15 each take one row of the tile: the intersections in the
     // reference's formula and edge rule, sorted ascending; then every lane reads its row's spans in pairs, left to right.
-    __device__ void poly_fill(int n, Rgba8 color, int mode) {
+    __device__ __forceinline__ void poly_fill(int n, Rgba8 color, int mode) {
         __syncthreads();
         if (tid < CV_TILE) {
             const float y = (float)(ty0 + tid);
             float min_y = s_vy[0], max_y = s_vy[0];
             for (int i = 1; i < n; ++i) { min_y = fminf(min_y, s_vy[i]); max_y = fmaxf(max_y, s_vy[i]); }
             const float start_y = fmaxf(0.0f, floorf(min_y)), end_y = fminf(frows - 1, ceilf(max_y));
-            float *xs = s_ix + tid * 64;
+            float *xs = s_ix + tid * CV_POINTS;
             int count = 0;
             if (y >= start_y && y <= end_y) {
                 for (int i = 0; i < n; ++i) {
@@ -329,7 +389,7 @@ template <int PIX> struct Cv {
         }
         __syncthreads();
         const int count = s_icnt[tid >> 4];
-        const float *xs = s_ix + (tid >> 4) * 64;
+        const float *xs = s_ix + (tid >> 4) * CV_POINTS;
         for (int i = 0; i + 1 < count; i += 2) {
             const float left_edge = xs[i], right_edge = xs[i + 1];
             if (mode == ZG_DRAW_SOFT) {
@@ -349,7 +409,7 @@ template <int PIX> struct Cv {
     }
 
     // drawLineBresenham (:187-240)
-    __device__ void line_bresenham(float p1x, float p1y, float p2x, float p2y, Rgba8 color) {
+    __device__ __forceinline__ void line_bresenham(float p1x, float p1y, float p2x, float p2y, Rgba8 color) {
         const int x1 = (int)p1x, y1 = (int)p1y, x2 = (int)p2x, y2 = (int)p2y;
         if (y1 == y2) {
             span((float)min(x1, x2), (float)max(x1, x2), (float)y1, color);
@@ -374,7 +434,7 @@ template <int PIX> struct Cv {
 
     // drawLineXiaolinWu (:246-341): end point 1 (two pixels), end point 2 (two pixels), then the main loop's two pixels of this lane's column
     // (row, when steep), each applied when it names this pixel — a line whose end points round to one column blends that column twice.
-    __device__ void line_wu(float x1, float y1, float x2, float y2, Rgba8 c2) {
+    __device__ __forceinline__ void line_wu(float x1, float y1, float x2, float y2, Rgba8 c2) {
         if (fabsf(y2 - y1) < 0.01f) {
             const float y = roundf(y1), min_x = fminf(x1, x2), max_x = fmaxf(x1, x2);
             const float left_x = floorf(min_x), right_x = ceilf(max_x);
@@ -411,7 +471,7 @@ template <int PIX> struct Cv {
         else { point(major, intery, cv_fade(c2, cv_rfpart(intery))); point(major, floorf(intery) + 1, cv_fade(c2, cv_fpart(intery))); }
     }
 
-    __device__ static float perpendicular_alpha(float sample, float center, float half_width) { // :491-496
+    __device__ __forceinline__ static float perpendicular_alpha(float sample, float center, float half_width) { // :491-496
         const float dist = fabsf(sample - center);
         if (dist > half_width + 0.5f) return 0.0f;
         if (dist > half_width - 0.5f) return half_width + 0.5f - dist;
@@ -419,7 +479,7 @@ template <int PIX> struct Cv {
     }
 
     // drawLine (:152-181) and everything under it
-    __device__ void line(float p1x, float p1y, float p2x, float p2y, Rgba8 color, uint32_t width, int mode) {
+    __device__ __forceinline__ void line(float p1x, float p1y, float p2x, float p2y, Rgba8 color, uint32_t width, int mode) {
         { // the tile against the segment: nothing the line writes is farther from it than `pad`
             const float pad = cv_line_pad(p1x, p1y, p2x, p2y, width, mode);
             if (cv_far_from_segment((float)tx0 + 7.5f, (float)ty0 + 7.5f, p1x, p1y, p2x, p2y, pad + CV_TILE_REACH + 0.5f)) return;
@@ -482,23 +542,135 @@ template <int PIX> struct Cv {
         if (alpha > 0) pixel(cv_fade(color, alpha));
     }
 
+    // evalQuadraticBezier (:1360-1368) and evalCubicBezier (:1373-1383), the sums left to right as written
+    __device__ __forceinline__ static CvPoint eval_quadratic(CvPoint p0, CvPoint p1, CvPoint p2, float t) {
+        const float u = 1.0f - t, uu = u * u, tt = t * t;
+        return {uu * p0.x + 2.0f * u * t * p1.x + tt * p2.x, uu * p0.y + 2.0f * u * t * p1.y + tt * p2.y};
+    }
+    __device__ __forceinline__ static CvPoint eval_cubic(CvPoint p0, CvPoint p1, CvPoint p2, CvPoint p3, float t) {
+        const float u = 1.0f - t, uu = u * u, uuu = uu * u, tt = t * t, ttt = tt * t;
+        return {uuu * p0.x + 3.0f * uu * t * p1.x + 3.0f * u * tt * p2.x + ttt * p3.x,
+                uuu * p0.y + 3.0f * uu * t * p1.y + 3.0f * u * tt * p2.y + ttt * p3.y};
+    }
+    // tessellateBezier (:1407-1425): `segments` points at t = i / (segments - 1), one lane each, into s_vx / s_vy from `base` on.
+    // The caller's barrier comes before anything reads them.
+    __device__ __forceinline__ void tessellate(bool cubic, CvPoint p0, CvPoint p1, CvPoint p2, CvPoint p3, int segments, int base) {
+        if (tid < segments) {
+            const float t = (float)tid / (float)(segments - 1);
+            const CvPoint q = cubic ? eval_cubic(p0, p1, p2, p3, t) : eval_quadratic(p0, p1, p2, t);
+            s_vx[base + tid] = q.x; s_vy[base + tid] = q.y;
+        }
+    }
+    // Every kind that is one fillPolygon over points the lanes put into s_vx / s_vy, through one call of poly_fill: fillPolygon itself
+    // (:935-1017) and fillSplinePolygon (:1296-1355), every edge's points one after the other. Entered by all lanes together.
+    __device__ __forceinline__ void filled(const zg_draw_cmd &c, const float *vertices, Rgba8 color) {
+        const float *v = vertices + 2 * (size_t)c.first_vertex;
+        int n = (int)c.n_vertices;
+        __syncthreads(); // the previous user of s_vx / s_vy has read them
+        if (c.kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
+            if (n < 3) return;
+            int total = 0;
+            for (uint32_t i = 0; i < c.n_vertices; ++i) {
+                CvPoint p0, cp1, cp2, p1;
+                cv_spline_edge(v, c.n_vertices, i, c.p[0], p0, cp1, cp2, p1);
+                const int segments = cv_segments(cv_cubic_length(p0, cp1, cp2, p1), CV_PPS_FAST, CV_SPLINE_MIN_SEGMENTS, CV_SPLINE_MAX_SEGMENTS);
+                if (total + segments > CV_POINTS) break; // k_canvas_prep has skipped such a command: never taken
+                tessellate(true, p0, cp1, cp2, p1, segments, total);
+                total += segments;
+            }
+            n = total;
+        } else {
+            if (n < 3) return;
+            if (tid < n) { s_vx[tid] = v[2 * tid]; s_vy[tid] = v[2 * tid + 1]; }
+        }
+        poly_fill(n, color, c.mode);
+    }
+
+    // A value every lane holds alike, said so: line() branches round barriers on its arguments
+    __device__ __forceinline__ static float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+    // Every kind that is a sequence of drawLine calls, through one call of line() (the routine is large: one copy of it in the kernel):
+    // drawLine itself, drawRectangle (:590-601) and drawPolygon (:579-587) with their end points from the command, and the curves, whose
+    // points the lanes evaluate into LDS first — drawBezierTessellated (:1428-1455) for drawQuadraticBezier (:1221-1245) and
+    // drawCubicBezier (:1249-1275), and drawSplinePolygon (:1280-1291), one cubic per edge. Entered by all lanes together.
+    __device__ __forceinline__ void outline(const zg_draw_cmd &c, const float *vertices, Rgba8 color) {
+        const float *v = vertices + 2 * (size_t)c.first_vertex;
+        const bool curve = c.kind >= ZG_DRAW_QUAD_BEZIER, spline = c.kind == ZG_DRAW_SPLINE_POLYGON;
+        if (!c.width || (spline && c.n_vertices < 3)) return;
+        const uint32_t curves = spline ? c.n_vertices : 1u;
+        for (uint32_t e = 0; e < curves; ++e) {
+            uint32_t calls = c.kind == ZG_DRAW_LINE ? 1u : c.kind == ZG_DRAW_RECT ? 4u : c.n_vertices;
+            if (curve) {
+                CvPoint p0, p1, p2, p3;
+                int segments;
+                if (spline) cv_spline_edge(v, c.n_vertices, e, c.p[0], p0, p1, p2, p3);
+                else { p0 = {v[0], v[1]}; p1 = {v[2], v[3]}; p2 = {v[4], v[5]}; p3 = c.kind == ZG_DRAW_CUBIC_BEZIER ? CvPoint{v[6], v[7]} : p2; }
+                if (c.kind == ZG_DRAW_QUAD_BEZIER) { // estimateQuadraticBezierLength (:1388-1393)
+                    const float length = (cv_distance(p0, p2) + (cv_distance(p0, p1) + cv_distance(p1, p2))) / 2.0f;
+                    segments = cv_segments(length, CV_PPS_QUADRATIC, CV_QUADRATIC_MIN_SEGMENTS, CV_BEZIER_MAX_SEGMENTS);
+                } else {
+                    const float pps = (c.mode == ZG_DRAW_SOFT || c.width > 2) ? CV_PPS_SOFT : CV_PPS_FAST;
+                    segments = cv_segments(cv_cubic_length(p0, p1, p2, p3), pps, CV_SPLINE_MIN_SEGMENTS, CV_BEZIER_MAX_SEGMENTS);
+                }
+                __syncthreads(); // the previous user of s_vx / s_vy has read them
+                tessellate(c.kind != ZG_DRAW_QUAD_BEZIER, p0, p1, p2, p3, segments, CV_CURVE_BASE);
+                __syncthreads();
+                calls = (uint32_t)segments - 1u;
+            }
+            if (curve) { // one lane per segment asks what line() asks first, whether the segment can reach the tile, and only the ones that can are drawn
+                bool near = false;
+                if (tid < (int)calls) {
+                    const float ax = s_vx[CV_CURVE_BASE + tid], ay = s_vy[CV_CURVE_BASE + tid], bx = s_vx[CV_CURVE_BASE + tid + 1], by = s_vy[CV_CURVE_BASE + tid + 1];
+                    near = !cv_far_from_segment((float)tx0 + 7.5f, (float)ty0 + 7.5f, ax, ay, bx, by, cv_line_pad(ax, ay, bx, by, c.width, c.mode) + CV_TILE_REACH + 0.5f);
+                }
+                const unsigned long long ballot = __ballot(near);
+                if ((tid & 63) == 0) s_near[tid >> 6] = ballot;
+                __syncthreads();
+            }
+            unsigned long long near_bits = 0;
+            for (uint32_t i = 0; i < calls; ++i) {
+                if (curve) {
+                    if ((i & 63u) == 0) {
+                        const unsigned long long m = s_near[i >> 6];
+                        near_bits = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
+                    }
+                    if (!((near_bits >> (i & 63u)) & 1ull)) continue;
+                }
+                float ax, ay, bx, by;
+                if (curve) {
+                    ax = uniform(s_vx[CV_CURVE_BASE + i]); ay = uniform(s_vy[CV_CURVE_BASE + i]);
+                    bx = uniform(s_vx[CV_CURVE_BASE + i + 1]); by = uniform(s_vy[CV_CURVE_BASE + i + 1]);
+                } else if (c.kind == ZG_DRAW_LINE) {
+                    ax = c.p[0]; ay = c.p[1]; bx = c.p[2]; by = c.p[3];
+                } else if (c.kind == ZG_DRAW_RECT) { // corners (l, t) (r, t) (r, b) (l, b) with r and b one less than the rectangle's
+                    const uint32_t j = (i + 1u) & 3u;
+                    ax = (i == 1 || i == 2) ? c.p[2] - 1 : c.p[0]; ay = i >= 2 ? c.p[3] - 1 : c.p[1];
+                    bx = (j == 1 || j == 2) ? c.p[2] - 1 : c.p[0]; by = j >= 2 ? c.p[3] - 1 : c.p[1];
+                } else {
+                    const uint32_t j = i + 1 == c.n_vertices ? 0 : i + 1;
+                    ax = v[2 * i]; ay = v[2 * i + 1]; bx = v[2 * j]; by = v[2 * j + 1];
+                }
+                line(ax, ay, bx, by, color, c.width, c.mode);
+            }
+            if (curve) __syncthreads();
+        }
+    }
+
     // One command: the reference's public call
-    __device__ void apply(const zg_draw_cmd &c, const float *vertices) {
+    __device__ __forceinline__ void apply(const zg_draw_cmd &c, const float *vertices) {
         Rgba8 color;
         color[0] = c.color[0]; color[1] = c.color[1]; color[2] = c.color[2]; color[3] = c.color[3];
-        switch (c.kind) {
-        case ZG_DRAW_LINE:
-            if (c.width) line(c.p[0], c.p[1], c.p[2], c.p[3], color, c.width, c.mode);
-            break;
-        case ZG_DRAW_RECT: { // :590-601
-            if (!c.width) break;
-            const float l = c.p[0], t = c.p[1], r = c.p[2] - 1, b = c.p[3] - 1;
-            line(l, t, r, t, color, c.width, c.mode);
-            line(r, t, r, b, color, c.width, c.mode);
-            line(r, b, l, b, color, c.width, c.mode);
-            line(l, b, l, t, color, c.width, c.mode);
-            break;
+        const int kind = c.kind;
+        if (kind == ZG_DRAW_LINE || kind == ZG_DRAW_RECT || kind == ZG_DRAW_POLYGON || kind == ZG_DRAW_QUAD_BEZIER || kind == ZG_DRAW_CUBIC_BEZIER ||
+            kind == ZG_DRAW_SPLINE_POLYGON) {
+            outline(c, vertices, color);
+            return;
         }
+        if (kind == ZG_DRAW_FILL_POLYGON || kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
+            filled(c, vertices, color);
+            return;
+        }
+        switch (kind) {
         case ZG_DRAW_FILL_RECT:
             fill_rect(c.p[0], c.p[1], c.p[2], c.p[3], color, c.mode);
             break;
@@ -514,24 +686,6 @@ template <int PIX> struct Cv {
             if (c.mode == ZG_DRAW_SOFT) ring(c.p[0], c.p[1], 0.0f, c.p[2], color, ZG_DRAW_SOFT);
             else disc_fast(c.p[0], c.p[1], c.p[2], color);
             break;
-        case ZG_DRAW_POLYGON: { // :579-587
-            if (!c.width) break;
-            const float *v = vertices + 2 * (size_t)c.first_vertex;
-            for (uint32_t i = 0; i < c.n_vertices; ++i) {
-                const uint32_t j = i + 1 == c.n_vertices ? 0 : i + 1;
-                line(v[2 * i], v[2 * i + 1], v[2 * j], v[2 * j + 1], color, c.width, c.mode);
-            }
-            break;
-        }
-        case ZG_DRAW_FILL_POLYGON: {
-            if (c.n_vertices < 3) break;
-            if (tid < (int)c.n_vertices) {
-                s_vx[tid] = vertices[2 * (size_t)(c.first_vertex + tid)];
-                s_vy[tid] = vertices[2 * (size_t)(c.first_vertex + tid) + 1];
-            }
-            poly_fill((int)c.n_vertices, color, c.mode);
-            break;
-        }
         }
     }
 };
@@ -541,9 +695,10 @@ __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmd
     using P = Px<PIX>;
     __shared__ uint16_t s_list[CV_CHUNK];
     __shared__ int s_wave_count[CV_CHUNK / 64];
-    __shared__ float s_vx[ZG_CANVAS_MAX_VERTICES], s_vy[ZG_CANVAS_MAX_VERTICES], s_ix[CV_TILE * ZG_CANVAS_MAX_VERTICES];
+    __shared__ float s_vx[CV_POINTS], s_vy[CV_POINTS], s_ix[CV_TILE * CV_POINTS];
     __shared__ float s_row[CV_TILE * 3];
     __shared__ int s_icnt[CV_TILE];
+    __shared__ unsigned long long s_near[4];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     Cv<PIX> cv;
     cv.tid = tid;
@@ -553,7 +708,7 @@ __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmd
     cv.inside = cv.col < img.cols && cv.row < img.rows;
     cv.dirty = false;
     cv.px = P::zero();
-    cv.s_vx = s_vx; cv.s_vy = s_vy; cv.s_ix = s_ix; cv.s_icnt = s_icnt; cv.s_row = s_row;
+    cv.s_vx = s_vx; cv.s_vy = s_vy; cv.s_ix = s_ix; cv.s_icnt = s_icnt; cv.s_row = s_row; cv.s_near = s_near;
     const size_t index = (size_t)cv.row * img.stride + (size_t)cv.col;
     bool loaded = false;
     // CV_CHUNK commands at a time, in CV_CHUNK / 256 slices of 256 (slice j: commands base + 256 j + tid): one pair of barriers per chunk
@@ -679,8 +834,9 @@ int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n
     for (uint32_t i = 0; i < n; ++i) {
         const int bad = cv_check(cmds[i], vertices, n_vertices);
         ZG_REQUIRE(bad != 2, ZG_ERR_UNSUPPORTED, "canvas_draw: command %u is a polygon of %u vertices (at most %u)", i, cmds[i].n_vertices, ZG_CANVAS_MAX_VERTICES);
+        ZG_REQUIRE(bad != 3, ZG_ERR_UNSUPPORTED, "canvas_draw: command %u is a filled spline polygon of more than %u points", i, ZG_CANVAS_MAX_CURVE_POINTS);
         ZG_REQUIRE(bad == 0, ZG_ERR_INVALID_ARGUMENT,
-                   "canvas_draw: command %u is outside the contract (kind, mode, finite parameters of magnitude <= %g, width <= %u, vertex range)", i,
+                   "canvas_draw: command %u is outside the contract (kind, mode, finite parameters of magnitude <= %g, width <= %u, vertex range or count)", i,
                    (double)ZG_CANVAS_MAX_COORD, ZG_CANVAS_MAX_WIDTH);
     }
     if (n == 0) return ZG_OK;
