@@ -543,9 +543,9 @@ def test_blur_and_half_resize_into_out(oracle, case, entry):
 @pytest.mark.parametrize("src_shift", (0, 4, 8))
 @pytest.mark.parametrize("kind", ("u8", "f32"))
 def test_isef_smooth_planes_at_every_origin(oracle, kind, src_shift, dst_shift):
-    """isef_smooth takes contiguous planes only (edges.hip, zg_isef_smooth: a strided view is refused as unsupported, checked last), so its
+    """isef_smooth takes contiguous planes only (isef.hip, zg_isef_smooth: a strided view is refused as unsupported, checked last), so its
     planes sit contiguous inside sentinel frames with the origin moved by one and two dwords: the u8 route's predicate is
-    source origin & 15 and destination origin & 15 (edges.hip, "isef_2d also wants a 16-byte aligned destination")."""
+    source origin & 15 and destination origin & 15 (isef.hip, "isef_2d also wants a 16-byte aligned destination")."""
     rows, cols = 272, 272
     host = host_of(oracle, kind, (rows, cols), seed=3)
     src = Batch((rows, cols), 512 + src_shift, torch.uint8 if kind == "u8" else torch.float32)

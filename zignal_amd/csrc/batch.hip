@@ -27,17 +27,13 @@ struct Frames { // n equally shaped frames back to back
 };
 
 // the integer taps convolveSeparable derives from gaussianBlur's f32 taps (convolution.zig:303-309), when the kernel is short
+// All of them: the batch routes do not drop the outer taps that rounded to zero (a known follow-up: DESIGN.md §1, the batch row).
 int gaussian_taps_u8(float sigma, std::vector<int32_t> &taps) {
-    taps.clear();
-    float f[255];
-    int n = zg_gaussian_kernel(sigma, nullptr, 0);
-    if (n < 0) return -n;
-    if (n > 255) return ZG_OK; // long kernels: the per-frame path
-    n = zg_gaussian_kernel(sigma, f, 255);
-    if (n < 0) return -n;
-    taps.resize((size_t)n);
-    for (int i = 0; i < n; ++i) taps[(size_t)i] = (int32_t)std::round(f[i] * 256.0f);
-    return ZG_OK;
+    taps.resize(255);
+    GaussianTapsI32 t;
+    const int rc = gaussian_taps_i32(sigma, taps.data(), 255, t);
+    taps.resize(rc == ZG_OK && t.n <= 255 ? (size_t)t.n : 0); // long kernels: the per-frame path
+    return rc;
 }
 
 int apply_shape(const zg_step &st, Frames &f) { // what a step does to shape and type; validates the step
@@ -311,13 +307,8 @@ int zg_batch_blur_resize(const void *src_frames, uint32_t n_frames, uint32_t row
     // integer taps exactly as convolveSeparable derives them (convolution.zig:303-309) from gaussianBlur's f32 taps
     std::vector<int32_t> taps;
     if (sigma > 0 && pixel == ZG_PIXEL_RGBA_U8) {
-        float f[255];
-        int n = zg_gaussian_kernel(sigma, nullptr, 0);
-        if (n < 0) return -n;
-        if (n <= 255) n = zg_gaussian_kernel(sigma, f, 255); // longer kernels take the general per-frame path below
-        if (n < 0) return -n;
-        if (n <= 255) taps.resize((size_t)n);
-        for (size_t i = 0; i < taps.size(); ++i) taps[i] = (int32_t)std::round(f[i] * 256.0f);
+        if (const int rc = gaussian_taps_u8(sigma, taps)) return rc; // empty for kernels past 255 taps: they take the general per-frame path below
+        const int n = (int)taps.size();
         const bool half = method->kind == ZG_INTERP_BILINEAR && rows == 2 * out_rows && cols == 2 * out_cols;
         if (half && !taps.empty()) {
             const StreamJob job{src_frames, dst_frames, n_frames, rows, cols, 4, (size_t)cols * 4, (size_t)out_cols * 4, in_px * 4, out_px * 4, true};

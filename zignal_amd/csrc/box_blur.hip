@@ -592,7 +592,7 @@ __global__ __launch_bounds__(SAT_THREADS) void k_sat_chain_planes(SatPlanes pl, 
 }
 
 // Integral image(s) of `src` (Image(T).Integral.compute, integral.zig:95-140): one f32 plane of rows x cols per channel,
-// planar, in the reference's association order. Also used by the Shen-Castan detector (edges.hip).
+// planar, in the reference's association order. Also used by the Shen-Castan detector (shen_castan.hip).
 // `integer_valued`: the caller knows every element is an integer in [0, 255] (always true for u8 pixels), which makes the
 // row sums exact and lets the row pass run as a parallel scan.
 // Exact-row sources take the fused pair of kernels, which can leave a gap between the planes (see sat_plane_stride).

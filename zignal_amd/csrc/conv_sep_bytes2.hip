@@ -735,22 +735,15 @@ int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const flo
     for (uint32_t i = 0; i < n && np < PYR_MAX_JOBS; ++i) {
         const zg_image &lv = levels[i];
         if (!(sigmas[i] > 0.5f) || lv.pixel != ZG_PIXEL_U8 || lv.rows == 0 || lv.cols == 0 || lv.rows > src->rows || lv.cols > src->cols) continue;
-        const int nfull = zg_gaussian_kernel(sigmas[i], nullptr, 0);
-        if (nfull < 1 || nfull > 65) continue;
-        float ft[65];
-        if (zg_gaussian_kernel(sigmas[i], ft, 65) != nfull) continue;
         int32_t it[65];
-        int64_t sum = 0;
-        bool ok = true;
-        for (int j = 0; j < nfull; ++j) { it[j] = (int32_t)std::round(ft[j] * 256.0f); ok = ok && it[j] >= 0 && it[j] <= 255; sum += it[j]; }
-        if (!ok || sum > 257) continue;
-        int z = 0;
-        while (nfull - 2 * z > 2 && it[z] == 0 && it[nfull - 1 - z] == 0) ++z;
-        const int nk = nfull - 2 * z;
+        GaussianTapsI32 t;
+        if (gaussian_taps_i32(sigmas[i], it, 65, t) != ZG_OK || t.n > 65) continue;
+        if (!t.bytes || t.sum > 257) continue;
+        const int z = t.z, nk = t.n - 2 * z;
         if (nk <= 7 || nk > 33 || !(nk & 1)) continue;
         Plan &p = plan[np];
         p.level = i; p.nk = nk; p.half = nk / 2; p.hp = std::max(4, (p.half + 3) / 4 * 4);
-        p.wide = sum * sum * 255 + 32768 >= 256 * 65536;
+        p.wide = t.sum * t.sum * 255 + 32768 >= 256 * 65536;
         p.fused = src->cols >= 2 * lv.cols;
         if (handled[i] || (which == 0 && !p.fused) || (which == 1 && p.fused)) continue; // which: 0 = the fused levels, 1 = the dense ones, 2 = both
         if (!p.fused && (p.wide || nk > 21)) continue;      // the batched dense column pass: sums <= 256, <= 21 taps (a reduction below 2 has sigma < 2.8 x blur_sigma;

@@ -492,6 +492,13 @@ static int run_sep(const zg_image *src, const zg_image *dst, const SepPlan &p, i
     return launch_two_pass<PIX, MODE>(src, dst, p, border, s);
 }
 
+// The taps to drop from each end of an integer kernel: outer pairs that are both zero, as long as more than two taps stay.
+static int zero_ends(const int32_t *k, int n) {
+    int z = 0;
+    while (n - 2 * z > 2 && k[z] == 0 && k[n - 1 - z] == 0) ++z;
+    return z;
+}
+
 static int conv_separable_impl(const zg_image *src, const zg_image *dst, const float *kx, uint32_t nkx,
                                const float *ky, uint32_t nky, int border, hipStream_t s) {
     int rc;
@@ -546,8 +553,7 @@ static int conv_separable_impl(const zg_image *src, const zg_image *dst, const f
         // Outer taps that round to zero add exactly nothing to an integer sum whatever the border rule hands them: drop them in pairs (the kernel stays
         // centred). gaussianBlur's 3-sigma radius leaves such taps from sigma 2.3 up (ORB's pyramid levels: 35 taps -> 29, 29 -> 25, 19 -> 17, 9 -> 7).
         auto trim_zero_ends = [](std::vector<int32_t> &k, int &nk) {
-            int z = 0;
-            while (nk - 2 * z > 2 && k[(size_t)z] == 0 && k[(size_t)(nk - 1 - z)] == 0) ++z;
+            const int z = zero_ends(k.data(), nk);
             if (z) {
                 k.erase(k.begin(), k.begin() + z);
                 k.resize((size_t)(nk - 2 * z));
@@ -625,6 +631,33 @@ static int conv_separable_planes_impl(const zg_image *src, const zg_image *dst, 
     return ZG_OK;
 }
 
+// gaussianBlur's taps for a sigma > 0 (image.zig:973-990), sized by the kernel's own size query.
+static int gaussian_taps(float sigma, std::vector<float> &taps) {
+    const int n = zg_gaussian_kernel(sigma, nullptr, 0);
+    if (n < 0) return -n;
+    taps = std::vector<float>((size_t)n);
+    return zg_gaussian_kernel(sigma, taps.data(), (uint32_t)n) == n ? ZG_OK : ZG_ERR_INVALID_ARGUMENT;
+}
+
+// The same taps as convolveSeparable scales them for integer pixels: scaleKernelToInt (convolution.zig:303-309), @round(k * 256).
+// The one derivation behind every u8 Gaussian route that does not go through conv_separable_impl; the routes' own limits (lengths,
+// tap range, sum) stay with the routes.
+int gaussian_taps_i32(float sigma, int32_t *taps, int capacity, GaussianTapsI32 &out) {
+    out = GaussianTapsI32{};
+    std::vector<float> f;
+    if (const int rc = gaussian_taps(sigma, f)) return rc;
+    out.n = (int)f.size();
+    if (out.n > capacity) return ZG_OK;
+    out.bytes = true;
+    for (int i = 0; i < out.n; ++i) {
+        taps[i] = (int32_t)std::round(f[(size_t)i] * 256.0f);
+        out.bytes = out.bytes && taps[i] >= 0 && taps[i] <= 255;
+        out.sum += taps[i];
+    }
+    out.z = zero_ends(taps, out.n);
+    return ZG_OK;
+}
+
 } // namespace zg
 
 using namespace zg;
@@ -668,14 +701,6 @@ int zg_gaussian_kernel(float sigma, float *taps, uint32_t capacity) {
     }
     for (uint32_t i = 0; i < size; ++i) taps[i] /= sum;
     return (int)size;
-}
-
-// gaussianBlur's taps for a sigma > 0 (image.zig:973-990), sized by the kernel's own size query.
-static int gaussian_taps(float sigma, std::vector<float> &taps) {
-    const int n = zg_gaussian_kernel(sigma, nullptr, 0);
-    if (n < 0) return -n;
-    taps = std::vector<float>((size_t)n);
-    return zg_gaussian_kernel(sigma, taps.data(), (uint32_t)n) == n ? ZG_OK : ZG_ERR_INVALID_ARGUMENT;
 }
 
 static int gaussian_impl(const zg_image *src, const zg_image *dst, float sigma, hipStream_t s) {

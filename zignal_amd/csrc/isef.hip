@@ -23,7 +23,9 @@
 // The forward and the backward pass of a direction run back to back in one launch (the backward pass reads what this workgroup's
 // storers wrote: a device-scope fence and a barrier between the two).
 // Round 3 ran the row passes as two full-plane transposes around a column kernel whose chain wave did its own LDS reads (64 per
-// block), the b * x products and a global store per row: 137 us per direction + 23 us per transpose for a 4096^2 plane.
+// block), the b * x products and a global store per row: 137 us per direction + 23 us per transpose for a 4096^2 plane. That route
+// (k_transpose_f32, k_isef_cols, at the end of the file) still takes the planes whose rows are not whole 16-byte chunks; isef_plane
+// chooses, and zg_isef_smooth exposes the smoothing for the bit-for-bit test.
 #include "zg_internal.h"
 
 #include <algorithm>
@@ -523,11 +525,176 @@ static void isef_2d_launch(const void *gray, float *sm, float *tmp, uint32_t *ch
 }
 
 // gray: the plane as f32, or — gray_is_bytes — as bytes (the detector's grey: integers 0 .. 255), converted as the row pass loads it.
-int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_t *check, uint32_t rows, uint32_t cols, float smooth, hipStream_t s) {
+static int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_t *check, uint32_t rows, uint32_t cols, float smooth, hipStream_t s) {
     if (!isef_2d_applies(rows, cols) || ((uintptr_t)gray & 15) || ((uintptr_t)sm & 15) || ((uintptr_t)tmp & 15)) return -1;
     if (gray_is_bytes) isef_2d_launch<true>(gray, sm, tmp, check, rows, cols, smooth, s);
     else isef_2d_launch<false>(gray, sm, tmp, check, rows, cols, smooth, s);
     return launch_ok();
 }
 
+// The recursions along ROWS run as the column kernel on the transposed plane: a row chain needs lanes = rows, i.e. a transpose
+// through LDS per 64-column chunk inside a kernel with one wave per 64 rows (354 + 464 us per 4096^2 plane that way); two plain
+// transposes at memory speed around the role-split column kernel do the same arithmetic, element for element, in a third of it.
+__global__ __launch_bounds__(256) void k_transpose_f32(const float *in, float *out, int rows, int cols) { // out[c][r] = in[r][c]
+    __shared__ float tile[64][65];
+    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64, lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int r = r0 + ly + 4 * k, c = c0 + lx;
+        tile[ly + 4 * k][lx] = in[(size_t)min(r, rows - 1) * cols + min(c, cols - 1)]; // clamped, unpredicated
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int c = c0 + ly + 4 * k, r = r0 + lx;
+        if (c < cols && r < rows) out[(size_t)c * rows + r] = tile[lx][ly + 4 * k];
+    }
+}
+// The same two recursions down / up the columns, in place on `data` with `temp` between them. One chain per column and two
+// dependent operations per row (a * run, then + b * x): a wave that also does its own loads and stores is latency-bound (one
+// wave per 64 columns: 379 us per 4096^2 plane). Roles are split as in box_blur.hip's k_sat_chain: a workgroup owns 64 columns;
+// waves 1..8 are LOADERS that keep six 64-row blocks in flight and hand rows over through an LDS ring, wave 0 is the CHAIN:
+// per row one LDS read, the recurrence, one store, nothing in its memory queue but stores. The up pass reads what the down
+// pass wrote (same workgroup, other waves): the chain wave publishes with a device-scope fence before the barrier that
+// separates the passes.
+__global__ __launch_bounds__(576) void k_isef_cols(float *data, float *temp, int rows, int cols, float b) {
+    constexpr int SB = 64, NL = 8, RL = SB / NL, D = 6;
+    __shared__ float ring[2][SB][64];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int c = blockIdx.x * 64 + lane;
+    const bool live = c < cols;
+    const int cc = min(c, cols - 1);
+    const int nblocks = (rows + SB - 1) / SB;
+    const float a = 1.0f - b;
+    const bool all_live = blockIdx.x * 64 + 64 <= (unsigned)cols; // workgroup-uniform
+
+    for (int pass = 0; pass < 2; ++pass) { // 0: down, data -> temp; 1: up, temp -> data. Block k of the up pass is block nblocks - 1 - k.
+        const float *in = pass == 0 ? data : temp;
+        float *out = pass == 0 ? temp : data;
+        if (wave == 0) {
+            float run = 0.0f;
+            for (int k = 0; k < nblocks; ++k) {
+                __syncthreads(); // block k of this pass is in ring[k & 1]
+                const int blk = pass == 0 ? k : nblocks - 1 - k, r0 = blk * SB;
+                float p[SB];
+#pragma unroll
+                for (int i = 0; i < SB; ++i) p[i] = ring[k & 1][i][lane];
+                float *o = out + (size_t)r0 * cols + cc;
+                const bool plain = all_live && r0 + SB <= rows; // every row of the block exists, every lane stores: no predicate
+                if (pass == 0 && plain && r0 > 0) {
+#pragma unroll
+                    for (int i = 0; i < SB; ++i) {
+                        const float bx = b * p[i], ar = a * run;
+                        run = bx + ar;
+                        o[(size_t)i * cols] = run;
+                    }
+                } else if (pass == 1 && plain && r0 + SB < rows) {
+#pragma unroll
+                    for (int i = SB - 1; i >= 0; --i) {
+                        const float bt = b * p[i], ar = a * run;
+                        run = bt + ar;
+                        o[(size_t)i * cols] = run;
+                    }
+                } else if (pass == 0) {
+#pragma unroll
+                    for (int i = 0; i < SB; ++i) {
+                        const float bx = b * p[i];
+                        if (r0 + i == 0) run = bx;
+                        else { const float ar = a * run; run = bx + ar; }
+                        if (live && r0 + i < rows) o[(size_t)i * cols] = run;
+                    }
+                } else {
+#pragma unroll
+                    for (int i = SB - 1; i >= 0; --i) {
+                        if (r0 + i < rows) { // rows past the end do not exist: the chain starts at rows - 1
+                            if (r0 + i == rows - 1) run = p[i];
+                            else { const float bt = b * p[i], ar = a * run; run = bt + ar; }
+                            if (live) o[(size_t)i * cols] = run;
+                        }
+                    }
+                }
+            }
+            if (pass == 0) __threadfence(); // temp is complete and visible before any loader of this workgroup reads it back
+        } else {
+            const int sub = wave - 1;
+            struct Regs { float v[RL]; };
+            auto fetch = [&](int k, Regs &g) { // clamped, unpredicated; steps past the last block re-read a valid row and are never used
+                const int blk = pass == 0 ? k : nblocks - 1 - k;
+                const int r0 = min(max(blk, 0), nblocks - 1) * SB + sub * RL;
+#pragma unroll
+                for (int i = 0; i < RL; ++i) g.v[i] = in[(size_t)min(r0 + i, rows - 1) * cols + cc];
+            };
+            auto publish = [&](int k, const Regs &g) {
+#pragma unroll
+                for (int i = 0; i < RL; ++i) ring[k & 1][sub * RL + i][lane] = g.v[i];
+            };
+            Regs g[D];
+#pragma unroll
+            for (int d = 0; d < D - 1; ++d) fetch(d, g[d]);
+            for (int k0 = 0; k0 < nblocks; k0 += D) {
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    const int k = k0 + d;
+                    if (k < nblocks) {
+                        fetch(k + D - 1, g[(d + D - 1) % D]);
+                        publish(k, g[d]);
+                        __syncthreads();
+                    }
+                }
+            }
+        }
+        __syncthreads(); // the pass is over for every wave (and the ring is free again)
+    }
+}
+
+// isefFilter2D (edges.zig:308-349): gray -> sm. The segmented recursions above (isef_2d) where their preconditions hold; planes whose rows are
+// not whole 16-byte chunks take round 3's route: transpose, column recursions on the cols x rows plane (in place on `t1`, `t2` between the
+// passes), transpose back into `sm`, then the columns proper. tmp, t1, t2: planes of the same size; check: isef_check_bytes().
+// gray8: the same plane as bytes, or null; gray (f32) may be null when gray8 is given and isef_2d_applies().
+void isef_plane(const float *gray, const uint8_t *gray8, float *sm, float *tmp, float *t1, float *t2, uint32_t *check, uint32_t rows, uint32_t cols, float smooth,
+                hipStream_t s) {
+    if (gray8 && isef_2d((const void *)gray8, true, sm, tmp, check, rows, cols, smooth, s) >= 0) return;
+    if (isef_2d((const void *)gray, false, sm, tmp, check, rows, cols, smooth, s) >= 0) return;
+    hipLaunchKernelGGL(k_transpose_f32, dim3(ceil_div(cols, 64), ceil_div(rows, 64)), dim3(256), 0, s, gray, t1, (int)rows, (int)cols);
+    hipLaunchKernelGGL(k_isef_cols, dim3(ceil_div(rows, 64)), dim3(576), 0, s, t1, t2, (int)cols, (int)rows, smooth);
+    hipLaunchKernelGGL(k_transpose_f32, dim3(ceil_div(rows, 64), ceil_div(cols, 64)), dim3(256), 0, s, (const float *)t1, sm, (int)cols, (int)rows);
+    hipLaunchKernelGGL(k_isef_cols, dim3(ceil_div(cols, 64)), dim3(576), 0, s, sm, tmp, (int)rows, (int)cols, smooth);
+}
+
 } // namespace zg
+
+using namespace zg;
+
+extern "C" {
+
+int zg_isef_smooth(const zg_image *src, const zg_image *dst, float smooth, zg_stream stream) {
+    ZG_REQUIRE(src && dst && src->data && dst->data, ZG_ERR_INVALID_ARGUMENT, "isef: null image");
+    ZG_REQUIRE((src->pixel == ZG_PIXEL_F32 || src->pixel == ZG_PIXEL_U8) && dst->pixel == ZG_PIXEL_F32, ZG_ERR_INVALID_ARGUMENT, "isef: an f32 or u8 plane into an f32 plane");
+    ZG_REQUIRE(src->rows == dst->rows && src->cols == dst->cols, ZG_ERR_DIMENSION_MISMATCH, "isef: %ux%u vs %ux%u", src->rows, src->cols, dst->rows, dst->cols);
+    ZG_REQUIRE(src->stride == src->cols && dst->stride == dst->cols, ZG_ERR_UNSUPPORTED, "isef: contiguous planes");
+    ZG_REQUIRE(smooth > 0 && smooth < 1, ZG_ERR_INVALID_ARGUMENT, "isef: InvalidBParameter (smooth %g not in (0, 1))", (double)smooth);
+    if (src->rows == 0 || src->cols == 0) return ZG_OK;
+    hipStream_t s = as_stream(stream);
+    const uint32_t rows = src->rows, cols = src->cols;
+    const size_t nf = ((size_t)rows * cols + 3) / 4 * 4;
+    ScratchBlock scratch(s);
+    if (const int rc = scratch.alloc(4 * nf * sizeof(float) + isef_check_bytes(rows, cols))) return rc;
+    float *tmp = (float *)scratch.p, *t1 = tmp + nf, *t2 = t1 + nf, *as_f32 = t2 + nf;
+    const float *gray = (const float *)src->data;
+    const uint8_t *gray8 = nullptr;
+    if (src->pixel == ZG_PIXEL_U8) { // as the detector has it: bytes for the segmented row pass, f32 only where that does not apply
+        gray8 = (const uint8_t *)src->data;
+        gray = nullptr;
+        // isef_2d also wants a 16-byte aligned destination; when it is not, isef_plane falls through to the transposing route, which reads the
+        // f32 plane: it has to exist then (the null plane was an illegal access)
+        if (!isef_2d_applies(rows, cols) || ((uintptr_t)gray8 & 15) || ((uintptr_t)dst->data & 15)) {
+            if (const int rc = canny_gray_plane(src, as_f32, nullptr, s)) return rc; // as(f32, u8)
+            gray = as_f32;
+            gray8 = nullptr;
+        }
+    }
+    isef_plane(gray, gray8, (float *)dst->data, tmp, t1, t2, (uint32_t *)(as_f32 + nf), rows, cols, smooth, s);
+    return launch_ok("e");
+}
+
+} // extern "C"

@@ -342,18 +342,11 @@ int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const floa
         // (profiles/r06_pyramid.txt). ZIGNAL_HIP_PYRAMID_TILE_MIN_RATIO moves the threshold (read once).
         static const float min_ratio = getenv("ZIGNAL_HIP_PYRAMID_TILE_MIN_RATIO") ? (float)atof(getenv("ZIGNAL_HIP_PYRAMID_TILE_MIN_RATIO")) : 1.3f;
         if (rx < min_ratio) continue;
-        const int nfull = zg_gaussian_kernel(sigmas[i], nullptr, 0);
-        if (nfull < 1 || nfull > 129) continue;
-        float ft[129];
-        if (zg_gaussian_kernel(sigmas[i], ft, 129) != nfull) continue;
         int32_t it[129];
-        int64_t sum = 0;
-        bool ok = true;
-        for (int j = 0; j < nfull; ++j) { it[j] = (int32_t)std::round(ft[j] * 256.0f); ok = ok && it[j] >= 0 && it[j] <= 255; sum += it[j]; } // scaleKernelToInt (convolution.zig:303-309)
-        if (!ok || sum > 257) continue; // a row sum must fit 16 bits: 255 x 257 = 65 535
-        int z = 0; // outer taps that rounded to zero add nothing
-        while (nfull - 2 * z > 2 && it[z] == 0 && it[nfull - 1 - z] == 0) ++z;
-        const int nk = nfull - 2 * z, half = nk / 2;
+        GaussianTapsI32 t;
+        if (gaussian_taps_i32(sigmas[i], it, 129, t) != ZG_OK || t.n > 129) continue;
+        if (!t.bytes || t.sum > 257) continue; // a row sum must fit 16 bits: 255 x 257 = 65 535
+        const int z = t.z, nk = t.n - 2 * z, half = nk / 2; // outer taps that rounded to zero add nothing
         if (!(nk & 1) || half > PT_MAX_HM || J.n == PT_MAX_JOBS) continue;
         int c = 0;
         while (classes[c] < half) ++c;
@@ -367,7 +360,7 @@ int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const floa
         job.rx = rx;
         job.ry = ry;
         job.hm = HM;
-        job.wide = sum > 256;
+        job.wide = t.sum > 256;
         // the staged rows of a tile: the tapped rows of th output rows (<= th ry + 2) + HM above and below + one to make the first row even
         job.th = std::max(1, (int)std::floor((float)(PT_SR - 2 * HM - 4) / ry));
         job.tiles_x = (int)ceil_div(lv.cols, (unsigned)PT_TW);

@@ -45,6 +45,15 @@ constexpr uint32_t SF_MAX_PLANES = 8; // planes per launch of conv_sep_tile_f32.
 int try_sep_tile_f32(const zg_image *src, const zg_image *dst, uint32_t n, const float *fx, const float *fy, int nk, uint32_t skipx, uint32_t skipy,
                      int border, hipStream_t s);                                                                                                          // conv_sep_tile_f32.hip
 
+// The integer taps every u8 Gaussian route multiplies by (conv_separable.hip): scaleKernelToInt of gaussianBlur's f32 taps.
+struct GaussianTapsI32 {
+    int n = 0;         // the full length, 2 ceil(3 sigma) + 1; the taps are written only when n <= capacity
+    int z = 0;         // outer taps that rounded to zero, per end: taps[z .. n - z) is the kernel the single-image routes run
+    int64_t sum = 0;   // of all taps
+    bool bytes = false; // every tap is in 0 .. 255
+};
+int gaussian_taps_i32(float sigma, int32_t *taps, int capacity, GaussianTapsI32 &out); // a status: a sigma zg_gaussian_kernel refuses is refused
+
 // u8 separable convolution of a batch of equally sized frames laid out back to back, one wave per column strip (conv_sep_stream.hip).
 struct StreamJob {
     const void *src; void *dst;
@@ -83,19 +92,24 @@ int motion_linear_frames(const zg_image *src, const zg_image *dst, uint32_t n, s
 int motion_radial_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float center_x, float center_y, float strength,
                          int spin, hipStream_t s);
 
-// ---- edges.hip
+// ---- edges.hip: sobel's batch entry, and what canny shares with shen_castan.hip (the grey plane also with isef.hip)
 int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
-int resize_impl_bilinear_u8(const zg_image *src, const zg_image *dst, hipStream_t s); // what zg_resize(.bilinear) runs for a u8 plane
+int canny_gray_plane(const zg_image *src, float *gray, uint8_t *gray8, hipStream_t s); // as(f32, convertColor(u8, px)) into gray, the same as bytes into gray8; either may be null
+size_t hysteresis_work_bytes(uint32_t rows, uint32_t cols);
+int run_hysteresis(uint8_t *state, uint32_t rows, uint32_t cols, char *work, const zg_image *dst, hipStream_t s, const char *who);
+int launch_emit(const uint8_t *state, int *label, const uint8_t *flag, const zg_image *dst, hipStream_t s);
 
 // ---- sobel_stream.hip
 int try_sobel_stream(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s);
 
 // ---- isef.hip
-int isef_2d(const void *gray, bool gray_is_bytes, float *sm, float *tmp, uint32_t *check, uint32_t rows, uint32_t cols, float smooth, hipStream_t s);
+void isef_plane(const float *gray, const uint8_t *gray8, float *sm, float *tmp, float *t1, float *t2, uint32_t *check, uint32_t rows, uint32_t cols, float smooth,
+                hipStream_t s);
 bool isef_2d_applies(uint32_t rows, uint32_t cols);
 size_t isef_check_bytes(uint32_t rows, uint32_t cols);
 
-// ---- the pyramid's levels
+// ---- the pyramid: pyramid.hip (the host side), conv_sep_bytes2.hip and pyramid_tile.hip (the kernels)
+int resize_impl_bilinear_u8(const zg_image *src, const zg_image *dst, hipStream_t s); // pyramid.hip: what zg_resize(.bilinear) runs for a u8 plane
 int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, int which, hipStream_t s); // conv_sep_bytes2.hip: several levels in three launches
 int try_pyramid_tiles_u8(const zg_image *src, const zg_image *levels, const float *sigmas, uint32_t n, uint8_t *handled, hipStream_t s); // pyramid_tile.hip: a level per kernel, nothing but the level written
 int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32_t *taps, int nk, hipStream_t s); // conv_sep_bytes2.hip: blur + bilinear level
