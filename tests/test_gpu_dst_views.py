@@ -475,8 +475,8 @@ Batch = V.Framed  # n contiguous frames inside a sentinel frame (Pipeline.run ta
 def test_pipeline_into_out(oracle, kind, rows, cols, pitch_is_16):
     """[blur 1.0, resize half, edges sobel] over 3 frames into out=, the batches contiguous inside sentinel frames (Pipeline.run takes
     contiguous batches, so the frame pitch follows from the shape). Rgba(u8) 34 x 268: frame pitches of 36448, 9112 and 2278 bytes, the first a
-    multiple of 16; Rgb(u8) 33 x 267: odd rows, pitches of 26433, 6384 and 2128 bytes, every frame-pitch term (src_frame % 16, dst_frame % 16:
-    conv_sep_stream.hip:462-468, conv_sep_bytes2.hip:860, sobel_stream.hip:229-230) on its slow side. The down2 store forms are reached by
+    multiple of 16; Rgb(u8) 33 x 267: odd rows, pitches of 26433, 6384 and 2128 bytes, every frame-pitch term (src_frame % 16, dst_frame % 16
+    in try_sep_stream, try_sep_bytes2_frames and try_sobel_stream) on its slow side. The down2 store forms are reached by
     test_blur_and_half_resize_into_out below (268 x 4 row bytes are no multiple of 32)."""
     ch = V.LAYOUT[kind][1]
     n, orows, ocols = 3, rows // 2, cols // 2
@@ -497,11 +497,12 @@ def test_pipeline_into_out(oracle, kind, rows, cols, pitch_is_16):
     assert_bits_equal(src.take(f"pipeline {kind} frames"), host, f"pipeline {kind}: the frames changed")
 
 
-# rows, cols, source shift, destination shift (bytes) -> the route of gaussianBlur + bilinear resize to half of Rgba(u8) frames:
-#   conv_sep_stream.hip:466  down2: rows % 2, rb % 32, dst_pitch % 8, dst_frame % 8, dst & 7 (after :462's rb % 16, src_frame % 16, src & 15)
-#   conv_sep_rgba8.hip:243   down2: rows % 2, cols % 4, dst_stride % 2, dst_frame_px % 2, dst & 7 (after :241's src_frame_px % 4, src & 15): what
-#                            zg_batch_blur_resize tries when the stream kernel refuses
-# Both entries call a half-size resize only when rows == 2 x out rows, so rows % 2 cannot be flipped inside either predicate: an odd-rows batch
+# rows, cols, source shift, destination shift (bytes) -> the route of gaussianBlur + bilinear resize to half of Rgba(u8) frames. Both entries
+# ask one list (batch.hip's gaussian_u8_routes) for the blur + 2:1 form, rb being the row bytes:
+#   try_sep_stream's down2 form:       rows % 2, rb % 32, dst pitch % 8, dst_frame % 8, dst & 7 (after rb % 16, src_frame % 16, src & 15)
+#   try_sep_rgba8_batch's down2 form:  rows % 2, cols % 4, dst stride % 2 pixels, dst_frame % 8, dst & 7 (after src_frame % 16, src & 15): what
+#                                      is tried when the stream kernel refuses
+# A half-size resize is one only when rows == 2 x out rows, so rows % 2 cannot be flipped inside either predicate: an odd-rows batch
 # is no half-size resize and takes the blur-then-resize route, which the 33-row case pins.
 HALF_CASES = {
     "stream_down2": (32, 272, 0, 0),     # rb = 1088: % 32 == 0, every term on its fast side
@@ -597,7 +598,7 @@ def test_host_band_layer_aliased(oracle):
 #                           already replaced"
 #   zg_runtime.cpp:438     "an in-place call (or any overlap) would have later bands read rows that earlier bands already overwrote" (the host
 #                           band layer: it steps aside and the whole-frame path runs; host images, so no device view is involved)
-#   edges.hip (sobel_impl) "in place on an Image(u8), or a destination view that shares bytes with the source: a lane reads its neighbours'
+#   edges.hip (sobel_frames) "in place on an Image(u8), or a destination view that shares bytes with the source: a lane reads its neighbours'
 #                           pixels, so the source is copied first"; canny and shen_castan read the source into scratch planes before any stage
 #                           writes the destination.
 # (a) out = the same view; (b) out = a view of the same canvas 3 rows down and 5 pixels right. Both equal the oracle run on a copy of the input:

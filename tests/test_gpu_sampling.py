@@ -566,7 +566,7 @@ def test_batch_pipeline_paths(oracle, case):
     n = 3
     if case == "half_sigma1":      # fused blur + 2:1 bilinear, 7 taps, zero-sum alpha handled like any channel
         rows, cols, orows, ocols, sigma, m, kind = 66, 320, 33, 160, 1.0, I.bilinear, "rgba_u8"
-    elif case == "third_bicubic":  # batched blur, then per-frame plane resize
+    elif case == "third_bicubic":  # batched blur, then the plane resize with the frame in the grid
         rows, cols, orows, ocols, sigma, m, kind = 60, 256, 20, 100, 0.6, I.bicubic, "rgba_u8"
     elif case == "odd_cols":       # cols % 4 != 0: general per-frame path
         rows, cols, orows, ocols, sigma, m, kind = 31, 131, 16, 65, 0.6, I.bilinear, "rgba_u8"

@@ -1,12 +1,13 @@
-// batch.hip — the `pipeline` recipe [blur gaussian sigma, resize] over a batch of frames (semantics of reference
-// src/cli/pipeline.zig:153-179 applied to N independent images laid out back to back). Frames are independent units:
-// this is also the shard a rank processes in the multi-GPU bench (no halo, no collective on the data path).
+// batch.hip — a recipe of steps (the CLI's `pipeline` command, reference src/cli/pipeline.zig:153-179) over N independent frames laid out back to
+// back. Frames are independent units: this is also the shard a rank processes in the multi-GPU bench (no halo, no collective on the data path).
 //
-// Result == Image.gaussianBlur followed by Image.resize on every frame (tests compare against exactly that).
-//   * Rgba(u8), bilinear to exactly half size, Gaussian-sized taps: ONE launch for the whole batch, blur and the 2:1
-//     bilinear fused (conv_sep_rgba8.hip); per frame the HBM traffic is the source read once + the small output.
-//   * Rgba(u8) otherwise: one batched blur launch into scratch frames, then resize per frame.
-//   * anything else: gaussianBlur + resize per frame.
+// Two entries, one runner (run_steps): zg_batch_pipeline takes any recipe, zg_batch_blur_resize is the recipe [gaussianBlur(sigma), resize] built on
+// the stack. The result of every step equals the Image method on every frame (the tests compare against exactly that).
+//   * run_steps walks the batch in groups whose intermediates fit two ping-pong scratch blocks, tries each step together with its successor
+//     (run_fused_pair) and then alone; a step is one launch over the group wherever its kernel takes the frame in its grid, frame by frame otherwise.
+//   * the u8 Gaussian has ONE route list, gaussian_u8_routes: the stream kernel (conv_sep_stream.hip), the tiled Rgba(u8) kernel (conv_sep_rgba8.hip),
+//     the two passes through u16 temp planes (conv_sep_bytes2.hip). [blur, resize(.bilinear) to exactly half] of Rgba(u8) frames asks the same list
+//     for its blur + 2:1 form (one launch, the blurred frames never written); everything else is the blur, then resize_frames.
 #include "zg_internal.h"
 
 #include <algorithm>
@@ -18,25 +19,14 @@ namespace zg {
 
 namespace {
 
-struct Frames { // n equally shaped frames back to back
-    void *data;
-    uint32_t n, rows, cols;
+struct Shape { // of the frames between two steps: what apply_shape tracks
+    uint32_t rows, cols;
     int pixel, space;
     size_t frame_bytes() const { return (size_t)rows * cols * pixel_size(pixel); }
-    zg_image frame(uint32_t i) const { return zg_image{(char *)data + (size_t)i * frame_bytes(), cols, rows, cols, pixel}; }
+    zg_image at(void *data) const { return zg_image{data, cols, rows, cols, pixel}; }
 };
 
-// the integer taps convolveSeparable derives from gaussianBlur's f32 taps (convolution.zig:303-309), when the kernel is short
-// All of them: the batch routes do not drop the outer taps that rounded to zero (a known follow-up: DESIGN.md §1, the batch row).
-int gaussian_taps_u8(float sigma, std::vector<int32_t> &taps) {
-    taps.resize(255);
-    GaussianTapsI32 t;
-    const int rc = gaussian_taps_i32(sigma, taps.data(), 255, t);
-    taps.resize(rc == ZG_OK && t.n <= 255 ? (size_t)t.n : 0); // long kernels: the per-frame path
-    return rc;
-}
-
-int apply_shape(const zg_step &st, Frames &f) { // what a step does to shape and type; validates the step
+int apply_shape(const zg_step &st, Shape &f) { // what a step does to shape and type; validates the step
     switch (st.kind) {
     case ZG_STEP_GAUSSIAN_BLUR:
         ZG_REQUIRE(st.sigma >= 0, ZG_ERR_INVALID_ARGUMENT, "pipeline: InvalidSigma (%g)", st.sigma);
@@ -69,52 +59,58 @@ int apply_shape(const zg_step &st, Frames &f) { // what a step does to shape and
     return ZG_ERR_INVALID_ARGUMENT;
 }
 
-int per_frame(const Frames &in, const Frames &out, const std::function<int(const zg_image *, const zg_image *)> &op) {
-    for (uint32_t i = 0; i < in.n; ++i) {
-        const zg_image a = in.frame(i), b = out.frame(i);
-        if (const int rc = op(&a, &b)) return rc;
+int per_frame(const FrameBatch &b, const std::function<int(const zg_image *, const zg_image *)> &op) {
+    zg_image src = *b.src, dst = *b.dst;
+    for (uint32_t i = 0; i < b.n; ++i) {
+        src.data = (char *)b.src->data + (size_t)i * b.src_frame;
+        dst.data = (char *)b.dst->data + (size_t)i * b.dst_frame;
+        if (const int rc = op(&src, &dst)) return rc;
     }
     return ZG_OK;
 }
 
-int run_blur(const Frames &in, const Frames &out, float sigma, hipStream_t s) {
-    if (sigma == 0) { ZG_HIP(hipMemcpyAsync(out.data, in.data, in.n * in.frame_bytes(), hipMemcpyDeviceToDevice, s)); return ZG_OK; } // image.zig:966
-    if (!pixel_is_float(in.pixel)) {
-        std::vector<int32_t> taps;
-        if (const int rc = gaussian_taps_u8(sigma, taps)) return rc;
-        if (!taps.empty()) {
-            const size_t sp = pixel_size(in.pixel);
-            const StreamJob job{in.data, out.data, in.n, in.rows, in.cols, (int)sp, in.cols * sp, in.cols * sp, in.frame_bytes(), in.frame_bytes(), false};
-            const int rc = try_sep_stream(job, taps.data(), taps.data(), (int)taps.size(), ZG_BORDER_MIRROR, s);
-            if (rc >= 0) return rc;
-            if (in.n > 1) { // longer kernels: the two passes through the u16 temp planes, the frame in the grid
-                const zg_image a = in.frame(0), b = out.frame(0);
-                const int rc2 = try_sep_bytes2_frames(&a, &b, in.n, in.frame_bytes(), in.frame_bytes(), taps.data(), (int)taps.size(), taps.data(),
-                                                      (int)taps.size(), ZG_BORDER_MIRROR, s);
-                if (rc2 >= 0) return rc2;
-            }
-        }
-    }
-    return per_frame(in, out, [&](const zg_image *a, const zg_image *b) { return zg_gaussian_blur(a, b, sigma, (zg_stream)s); });
+// The routes of gaussianBlur(sigma) on u8 frames that take the batch in their grid, in the order they are tried; -1 when none applies (the
+// caller goes frame by frame). A destination of exactly half the source asks for blur + 2:1 bilinear, which the first two have a form for.
+//   1. try_sep_stream: 3 .. 9 taps while (taps / 2 + 1) x bytes per pixel <= 16, 16-byte rows.
+//   2. try_sep_rgba8_batch: Rgba(u8), 3 .. 9 taps, columns a multiple of 4. Both this and route 3 take the 9-tap Rgba(u8) blur that route 1
+//      refuses; this one first: 64 x 1080p at sigma 1.2 then a bicubic resize, 0.80 ms against 1.08 ms with route 3 first, through either
+//      entry (profiles/batch_one_runner.txt).
+//   3. try_sep_bytes2_frames: up to 65 taps through u16 temp planes, a batch only (one frame does better in zg_gaussian_blur, which drops
+//      the outer taps that rounded to zero).
+// The taps are the integers convolveSeparable derives from gaussianBlur's f32 taps (convolution.zig:303-309), all of them: the batch routes
+// do not drop the zero end taps (a known follow-up: DESIGN.md §1, the batch row).
+int gaussian_u8_routes(const FrameBatch &b, float sigma, hipStream_t s) {
+    int32_t taps[255];
+    GaussianTapsI32 t;
+    if (const int rc = gaussian_taps_i32(sigma, taps, 255, t)) return rc;
+    if (t.n > 255) return -1;
+    int rc = try_sep_stream(b, taps, taps, t.n, ZG_BORDER_MIRROR, s);
+    if (rc < 0) rc = try_sep_rgba8_batch(b, taps, taps, t.n, ZG_BORDER_MIRROR, s);
+    if (rc < 0 && b.n > 1) rc = try_sep_bytes2_frames(b, taps, t.n, taps, t.n, ZG_BORDER_MIRROR, s);
+    return rc;
 }
 
-int run_resize(const Frames &in, const Frames &out, const zg_method &method, hipStream_t s) {
-    if (in.n > 0) { // one launch over the batch wherever the path is a single kernel
-        const zg_image a = in.frame(0), b = out.frame(0);
-        const int rc = resize_frames(&a, &b, &method, in.n, in.frame_bytes(), out.frame_bytes(), s);
-        if (rc >= 0) return rc;
-    }
-    return per_frame(in, out, [&](const zg_image *a, const zg_image *b) { return resize_impl(a, b, &method, s); });
+int run_blur(const FrameBatch &b, float sigma, hipStream_t s) {
+    if (sigma == 0) { ZG_HIP(hipMemcpyAsync(b.dst->data, b.src->data, b.n * b.src_frame, hipMemcpyDeviceToDevice, s)); return ZG_OK; } // image.zig:966
+    if (!pixel_is_float(b.src->pixel))
+        if (const int rc = gaussian_u8_routes(b, sigma, s); rc >= 0) return rc;
+    return per_frame(b, [&](const zg_image *src, const zg_image *dst) { return zg_gaussian_blur(src, dst, sigma, (zg_stream)s); });
 }
 
-int run_convert(const Frames &in, const Frames &out, const float *lut, hipStream_t s) {
+int run_resize(const FrameBatch &b, const zg_method &method, hipStream_t s) {
+    if (const int rc = resize_frames(b, &method, s); rc >= 0) return rc; // one launch over the batch wherever the path is a single kernel
+    return per_frame(b, [&](const zg_image *src, const zg_image *dst) { return resize_impl(src, dst, &method, s); });
+}
+
+int run_convert(const FrameBatch &b, int src_space, int dst_space, const float *lut, hipStream_t s) {
     // per pixel, and the frames are contiguous: the batch is one tall image
-    const uint64_t tall = (uint64_t)in.rows * in.n;
+    const uint64_t tall = (uint64_t)b.src->rows * b.n;
     if (tall <= 0x7fffffffu) {
-        const zg_image a{in.data, in.cols, (uint32_t)tall, in.cols, in.pixel}, b{out.data, out.cols, (uint32_t)tall, out.cols, out.pixel};
-        return convert_impl(&a, in.space, &b, out.space, lut, s);
+        zg_image src = *b.src, dst = *b.dst;
+        src.rows = dst.rows = (uint32_t)tall;
+        return convert_impl(&src, src_space, &dst, dst_space, lut, s);
     }
-    return per_frame(in, out, [&](const zg_image *a, const zg_image *b) { return convert_impl(a, in.space, b, out.space, lut, s); });
+    return per_frame(b, [&](const zg_image *src, const zg_image *dst) { return convert_impl(src, src_space, dst, dst_space, lut, s); });
 }
 
 // The CLI's edges step (src/cli/edges.zig:126-135): gray = frame.convert(u8); detector(gray) -> Image(u8); .convert(frame type). The
@@ -123,62 +119,121 @@ int run_convert(const Frames &in, const Frames &out, const float *lut, hipStream
 // That shortcut holds for u8 frames in Gray / Rgb / Rgba. Float frames do not: Image(f32).sobel works on the raw floats (edges.zig:36-45 casts, it does
 // not scale), where the bridge's frame.convert(u8) maps [0, 1] to [0, 255] first; and frames a CONVERT step left in another colour space (Oklab, Lab, Hsv ...)
 // are not RGB at all. Those frames go through the bridge literally: one conversion launch to a grey u8 plane, the detector on that.
-int run_edges(const zg_step &st, const Frames &in_frames, const Frames &out, hipStream_t s) {
+int run_edges(const zg_step &st, const FrameBatch &b, int space, hipStream_t s) {
     ScratchBlock grey(s), bridged(s); // released in the reverse order
-    const size_t plane = (size_t)in_frames.rows * in_frames.cols;
-    if (const int rc = grey.alloc(plane * in_frames.n)) return rc;
-    Frames in = in_frames;
-    const bool direct = !pixel_is_float(in.pixel) && (in.space == ZG_CS_GRAY || in.space == ZG_CS_RGB || in.space == ZG_CS_RGBA);
+    const Shape plane{b.src->rows, b.src->cols, ZG_PIXEL_U8, ZG_CS_GRAY};
+    if (const int rc = grey.alloc(plane.frame_bytes() * b.n)) return rc;
+    const zg_image g0 = plane.at(grey.p);
+    zg_image bridge0{};
+    FrameBatch in{b.src, &g0, b.n, b.src_frame, plane.frame_bytes()};
+    const bool direct = !pixel_is_float(b.src->pixel) && (space == ZG_CS_GRAY || space == ZG_CS_RGB || space == ZG_CS_RGBA);
     if (!direct) {
-        if (const int rc = bridged.alloc(plane * in.n)) return rc;
-        const Frames b8{bridged.p, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
-        if (const int rc = run_convert(in, b8, nullptr, s)) return rc;
-        in = b8;
+        if (const int rc = bridged.alloc(plane.frame_bytes() * b.n)) return rc;
+        bridge0 = plane.at(bridged.p);
+        if (const int rc = run_convert(FrameBatch{b.src, &bridge0, b.n, b.src_frame, plane.frame_bytes()}, space, ZG_CS_GRAY, nullptr, s)) return rc;
+        in.src = &bridge0;
+        in.src_frame = plane.frame_bytes();
     }
-    const Frames g{grey.p, in.n, in.rows, in.cols, ZG_PIXEL_U8, ZG_CS_GRAY};
-    int rc = -1;
-    if (st.edges == ZG_EDGES_SOBEL && in.n > 0) {
-        const zg_image a = in.frame(0), b = g.frame(0);
-        rc = sobel_frames(&a, &b, in.n, in.frame_bytes(), plane, s); // one launch over the batch
-    }
+    int rc = st.edges == ZG_EDGES_SOBEL ? sobel_frames(in, s) : -1; // one launch over the batch
     if (rc == -1)
-        rc = per_frame(in, g, [&](const zg_image *a, const zg_image *b) {
-            if (st.edges == ZG_EDGES_SOBEL) return zg_sobel(a, b, (zg_stream)s);
-            if (st.edges == ZG_EDGES_CANNY) return zg_canny(a, b, st.sigma, st.low, st.high, (zg_stream)s);
-            return zg_shen_castan(a, b, st.sigma, st.window, st.high, st.low, 1, st.use_nms, (zg_stream)s);
+        rc = per_frame(in, [&](const zg_image *src, const zg_image *dst) {
+            if (st.edges == ZG_EDGES_SOBEL) return zg_sobel(src, dst, (zg_stream)s);
+            if (st.edges == ZG_EDGES_CANNY) return zg_canny(src, dst, st.sigma, st.low, st.high, (zg_stream)s);
+            return zg_shen_castan(src, dst, st.sigma, st.window, st.high, st.low, 1, st.use_nms, (zg_stream)s);
         });
-    if (rc == ZG_OK) rc = run_convert(g, out, nullptr, s);
+    if (rc == ZG_OK) rc = run_convert(FrameBatch{&g0, b.dst, b.n, plane.frame_bytes(), b.dst_frame}, ZG_CS_GRAY, space, nullptr, s);
     return rc;
 }
 
-// motion blur and box blur over the batch: the frame index is in the grid (round 5; they launched once per frame before)
-int run_motion(const zg_step &st, const Frames &in, const Frames &out, hipStream_t s) {
-    if (in.n == 0) return ZG_OK;
-    const zg_image a = in.frame(0), b = out.frame(0);
-    if (st.motion == ZG_MOTION_LINEAR) return motion_linear_frames(&a, &b, in.n, in.frame_bytes(), out.frame_bytes(), st.cos_a, st.sin_a, st.distance, s);
-    return motion_radial_frames(&a, &b, in.n, in.frame_bytes(), out.frame_bytes(), st.center_x, st.center_y, st.strength, st.motion == ZG_MOTION_RADIAL_SPIN, s);
-}
-int run_box(const zg_step &st, const Frames &in, const Frames &out, hipStream_t s) {
-    if (in.n == 0) return ZG_OK;
-    const zg_image a = in.frame(0), b = out.frame(0);
-    return box_blur_frames(&a, &b, in.n, in.frame_bytes(), out.frame_bytes(), st.radius, s);
+// one step over the batch. Motion blur, box blur and warp carry the frame index in the grid (round 5; they launched once per frame before).
+int run_step(const zg_step &st, const FrameBatch &b, int src_space, int dst_space, hipStream_t s) {
+    switch (st.kind) {
+    case ZG_STEP_GAUSSIAN_BLUR: return run_blur(b, st.sigma, s);
+    case ZG_STEP_BOX_BLUR: return box_blur_frames(b, st.radius, s);
+    case ZG_STEP_RESIZE: return run_resize(b, st.method, s);
+    case ZG_STEP_CONVERT: return run_convert(b, src_space, dst_space, st.srgb_lut, s);
+    case ZG_STEP_MEDIAN_BLUR:
+        return per_frame(b, [&](const zg_image *src, const zg_image *dst) { return zg_order_statistic_blur(src, dst, st.radius, 0, 0.5, ZG_BORDER_MIRROR, (zg_stream)s); });
+    case ZG_STEP_MOTION_BLUR:
+        if (st.motion == ZG_MOTION_LINEAR) return motion_linear_frames(b, st.cos_a, st.sin_a, st.distance, s);
+        return motion_radial_frames(b, st.center_x, st.center_y, st.strength, st.motion == ZG_MOTION_RADIAL_SPIN, s);
+    case ZG_STEP_EDGES: return run_edges(st, b, src_space, s);
+    default: { // warp: the same map for every frame, one launch
+        const int rc = warp_frames(b, st.transform, st.m, &st.method, s);
+        if (rc != -1) return rc; // -1: more frames than one launch takes, frame by frame
+        return per_frame(b, [&](const zg_image *src, const zg_image *dst) { return zg_warp(src, dst, st.transform, st.m, &st.method, (zg_stream)s); });
+    }
+    }
 }
 
-// steps [i, i + 2) as one fused launch over the batch, or -1
-int run_fused_pair(const zg_step &s0, const zg_step &s1, const Frames &in, const Frames &out, hipStream_t s) {
-    if (s0.kind == ZG_STEP_GAUSSIAN_BLUR && s1.kind == ZG_STEP_RESIZE && in.pixel == ZG_PIXEL_RGBA_U8 && s0.sigma > 0 && s1.method.kind == ZG_INTERP_BILINEAR &&
-        in.rows == 2 * out.rows && in.cols == 2 * out.cols) {
-        std::vector<int32_t> taps;
-        if (const int rc = gaussian_taps_u8(s0.sigma, taps)) return rc;
-        if (taps.empty()) return -1;
-        const StreamJob job{in.data, out.data, in.n, in.rows, in.cols, 4, (size_t)in.cols * 4, (size_t)out.cols * 4, in.frame_bytes(), out.frame_bytes(), true};
-        return try_sep_stream(job, taps.data(), taps.data(), (int)taps.size(), ZG_BORDER_MIRROR, s);
-    }
-    if (s0.kind == ZG_STEP_RESIZE && s1.kind == ZG_STEP_CONVERT && in.space == ZG_CS_RGBA && s0.method.kind == ZG_INTERP_BILINEAR && in.n > 0) {
-        const zg_image a = in.frame(0), b = out.frame(0);
-        return resize_convert_rgba8_frames(&a, &b, s1.dst_space, in.n, in.frame_bytes(), out.frame_bytes(), s1.srgb_lut, s);
-    }
+// two steps as one fused launch over the batch (b.dst has the second step's shape), or -1
+int run_fused_pair(const zg_step &s0, const zg_step &s1, const FrameBatch &b, int src_space, hipStream_t s) {
+    if (s0.kind == ZG_STEP_GAUSSIAN_BLUR && s1.kind == ZG_STEP_RESIZE && b.src->pixel == ZG_PIXEL_RGBA_U8 && s0.sigma > 0 && s1.method.kind == ZG_INTERP_BILINEAR &&
+        b.src->rows == 2 * b.dst->rows && b.src->cols == 2 * b.dst->cols)
+        return gaussian_u8_routes(b, s0.sigma, s);
+    if (s0.kind == ZG_STEP_RESIZE && s1.kind == ZG_STEP_CONVERT && src_space == ZG_CS_RGBA && s0.method.kind == ZG_INTERP_BILINEAR)
+        return resize_convert_rgba8_frames(b, s1.dst_space, s1.srgb_lut, s);
     return -1;
+}
+
+// The recipe over the batch, every argument already checked. Frames go through in groups: two ping-pong scratch blocks hold a group's
+// intermediates (a 1024-frame 1080p batch has 8.5 GB of them; nothing is gained by keeping more than a chip-filling group in flight). A block
+// takes at most a quarter of the scratch cache (512 MiB by default), so both stay cached from call to call beside whatever else lives there.
+int run_steps(const void *src_frames, uint32_t n_frames, const std::vector<Shape> &shape, const zg_step *steps, void *dst_frames, hipStream_t s) {
+    const uint32_t n_steps = (uint32_t)shape.size() - 1;
+    if (n_steps == 0) {
+        ZG_HIP(hipMemcpyAsync(dst_frames, src_frames, (size_t)n_frames * shape[0].frame_bytes(), hipMemcpyDeviceToDevice, s));
+        return ZG_OK;
+    }
+    if (n_steps == 2) { // a recipe that is one fused pair has no intermediates: no scratch and no groups, one launch over the batch
+        const zg_image a = shape[0].at((void *)src_frames), b = shape[2].at(dst_frames);
+        const int rc = run_fused_pair(steps[0], steps[1], FrameBatch{&a, &b, n_frames, shape[0].frame_bytes(), shape[2].frame_bytes()}, shape[0].space, s);
+        if (rc >= 0) return rc;
+    }
+    size_t widest = 0; // bytes per frame of the largest intermediate
+    for (uint32_t i = 1; i < n_steps; ++i) widest = std::max(widest, shape[i].frame_bytes());
+    const size_t budget = std::min<size_t>((size_t)1 << 30, scratch_block_budget());
+    const uint32_t group = widest ? (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, budget / widest)) : n_frames;
+    ScratchBlock ping[2]{ScratchBlock(s), ScratchBlock(s)};
+    int rc = ZG_OK;
+    if (widest) {
+        if ((rc = ping[0].alloc((size_t)group * widest))) return rc;
+        if (n_steps > 2 && (rc = ping[1].alloc((size_t)group * widest))) return rc;
+    }
+    for (uint32_t g0 = 0; g0 < n_frames && rc == ZG_OK; g0 += group) {
+        const uint32_t gn = std::min(group, n_frames - g0);
+        void *cur = (char *)src_frames + (size_t)g0 * shape[0].frame_bytes();
+        int flip = 0;
+        for (uint32_t i = 0; i < n_steps && rc == ZG_OK;) {
+            // steps [i, i + take) from `cur` into the caller's frames when they are the last, into a scratch block otherwise
+            auto run = [&](uint32_t take) {
+                const uint32_t o = i + take;
+                void *next = o == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[o].frame_bytes()) : (void *)ping[flip].p;
+                const zg_image a = shape[i].at(cur), b = shape[o].at(next);
+                const FrameBatch fb{&a, &b, gn, shape[i].frame_bytes(), shape[o].frame_bytes()};
+                const int r = take == 2 ? run_fused_pair(steps[i], steps[i + 1], fb, shape[i].space, s) : run_step(steps[i], fb, shape[i].space, shape[o].space, s);
+                if (r < 0) return r; // a pair that does not fuse
+                cur = next;
+                if (o != n_steps) flip ^= 1;
+                i = o;
+                return r;
+            };
+            rc = n_steps > 2 && i + 1 < n_steps ? run(2) : -1; // the step together with its successor (a two-step recipe's pair was tried above), then alone
+            if (rc < 0) rc = run(1);
+        }
+    }
+    ping[0].reset(); // the first block first (an array's destructors run from its end): the order of frees decides which block a captured graph reuses
+    return rc;
+}
+
+// the shapes after every step: validates all steps before anything is enqueued, like the CLI validates its recipe first (pipeline.zig:108-114)
+int shapes_of(const Shape &first, const zg_step *steps, uint32_t n_steps, std::vector<Shape> &shape) {
+    shape.assign(1, first);
+    for (uint32_t i = 0; i < n_steps; ++i) {
+        shape.push_back(shape.back());
+        if (const int rc = apply_shape(steps[i], shape.back())) return rc;
+    }
+    return ZG_OK;
 }
 
 } // namespace
@@ -194,13 +249,12 @@ int zg_batch_pipeline_shape(uint32_t rows, uint32_t cols, int pixel, int space, 
                             int *out_pixel, int *out_space) {
     ZG_REQUIRE(pixel_valid(pixel), ZG_ERR_INVALID_ARGUMENT, "pipeline: invalid pixel type %d", pixel);
     ZG_REQUIRE(n_steps == 0 || steps != nullptr, ZG_ERR_INVALID_ARGUMENT, "pipeline: null steps");
-    Frames f{nullptr, 0, rows, cols, pixel, space};
-    for (uint32_t i = 0; i < n_steps; ++i)
-        if (const int rc = apply_shape(steps[i], f)) return rc;
-    if (out_rows) *out_rows = f.rows;
-    if (out_cols) *out_cols = f.cols;
-    if (out_pixel) *out_pixel = f.pixel;
-    if (out_space) *out_space = f.space;
+    std::vector<Shape> shape;
+    if (const int rc = shapes_of(Shape{rows, cols, pixel, space}, steps, n_steps, shape)) return rc;
+    if (out_rows) *out_rows = shape.back().rows;
+    if (out_cols) *out_cols = shape.back().cols;
+    if (out_pixel) *out_pixel = shape.back().pixel;
+    if (out_space) *out_space = shape.back().space;
     return ZG_OK;
 }
 
@@ -212,85 +266,12 @@ int zg_batch_pipeline(const void *src_frames, uint32_t n_frames, uint32_t rows, 
     for (uint32_t i = 0; i < n_steps; ++i) // a step with a caller's table would upload it after earlier steps were enqueued: refused up front
         if ((steps[i].srgb_lut || steps[i].method.lanczos_lut) && refuse_under_capture(s, "zg_batch_pipeline with a caller's sRGB or Lanczos table in a step"))
             return ZG_ERR_UNSUPPORTED;
-    // shapes after every step (validates all steps before anything is enqueued, like the CLI validates its recipe first: pipeline.zig:108-114)
-    std::vector<Frames> shape(n_steps + 1);
-    shape[0] = Frames{nullptr, 0, rows, cols, pixel, space};
-    size_t widest = 0; // bytes per frame of the largest intermediate
-    for (uint32_t i = 0; i < n_steps; ++i) {
-        shape[i + 1] = shape[i];
-        if (const int rc = apply_shape(steps[i], shape[i + 1])) return rc;
-        if (i + 1 < n_steps) widest = std::max(widest, shape[i + 1].frame_bytes());
-    }
+    std::vector<Shape> shape;
+    if (const int rc = shapes_of(Shape{rows, cols, pixel, space}, steps, n_steps, shape)) return rc;
     if (n_frames == 0 || rows == 0 || cols == 0) return ZG_OK;
     ZG_REQUIRE(src_frames && dst_frames, ZG_ERR_INVALID_ARGUMENT, "pipeline: null frame pointer");
-    for (const Frames &f : shape) ZG_REQUIRE(f.rows > 0 && f.cols > 0, ZG_ERR_INVALID_ARGUMENT, "pipeline: a step produces empty frames");
-    if (n_steps == 0) {
-        ZG_HIP(hipMemcpyAsync(dst_frames, src_frames, (size_t)n_frames * shape[0].frame_bytes(), hipMemcpyDeviceToDevice, s));
-        return ZG_OK;
-    }
-    // Frames go through in groups: two ping-pong scratch blocks hold a group's intermediates (a 1024-frame 1080p batch has 8.5 GB of
-    // them; nothing is gained by keeping more than a chip-filling group in flight). A block takes at most a quarter of the scratch
-    // cache (512 MiB by default), so both stay cached from call to call beside whatever else lives there.
-    const size_t budget = std::min<size_t>((size_t)1 << 30, scratch_block_budget());
-    const uint32_t group = widest ? (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, budget / widest)) : n_frames;
-    ScratchBlock ping[2]{ScratchBlock(s), ScratchBlock(s)};
-    int rc = ZG_OK;
-    if (widest) {
-        if ((rc = ping[0].alloc((size_t)group * widest))) return rc;
-        if (n_steps > 2 && (rc = ping[1].alloc((size_t)group * widest))) return rc;
-    }
-    for (uint32_t g0 = 0; g0 < n_frames && rc == ZG_OK; g0 += group) {
-        const uint32_t gn = std::min(group, n_frames - g0);
-        Frames cur = shape[0];
-        cur.n = gn;
-        cur.data = (char *)src_frames + (size_t)g0 * shape[0].frame_bytes();
-        int flip = 0;
-        for (uint32_t i = 0; i < n_steps && rc == ZG_OK;) {
-            // try the step together with its successor
-            uint32_t take = 1;
-            if (i + 1 < n_steps) {
-                Frames two = shape[i + 2];
-                two.n = gn;
-                two.data = i + 2 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : (void *)ping[flip].p;
-                const int rf = run_fused_pair(steps[i], steps[i + 1], cur, two, s);
-                if (rf >= 0) {
-                    rc = rf;
-                    take = 2;
-                    cur = two;
-                    if (i + 2 != n_steps) flip ^= 1;
-                }
-            }
-            if (take == 1) {
-                Frames next = shape[i + 1];
-                next.n = gn;
-                next.data = i + 1 == n_steps ? (void *)((char *)dst_frames + (size_t)g0 * shape[n_steps].frame_bytes()) : (void *)ping[flip].p;
-                const zg_step &st = steps[i];
-                switch (st.kind) {
-                case ZG_STEP_GAUSSIAN_BLUR: rc = run_blur(cur, next, st.sigma, s); break;
-                case ZG_STEP_BOX_BLUR: rc = run_box(st, cur, next, as_stream(stream)); break;
-                case ZG_STEP_RESIZE: rc = run_resize(cur, next, st.method, s); break;
-                case ZG_STEP_CONVERT: rc = run_convert(cur, next, st.srgb_lut, s); break;
-                case ZG_STEP_MEDIAN_BLUR:
-                    rc = per_frame(cur, next, [&](const zg_image *a, const zg_image *b) { return zg_order_statistic_blur(a, b, st.radius, 0, 0.5, ZG_BORDER_MIRROR, stream); });
-                    break;
-                case ZG_STEP_MOTION_BLUR: rc = run_motion(st, cur, next, s); break;
-                case ZG_STEP_EDGES: rc = run_edges(st, cur, next, s); break;
-                default: { // warp: the same map for every frame, one launch
-                    const zg_image a = cur.frame(0), b = next.frame(0);
-                    rc = warp_frames(&a, &b, st.transform, st.m, &st.method, gn, cur.frame_bytes(), next.frame_bytes(), s);
-                    if (rc == -1) // more frames than one launch takes: frame by frame
-                        rc = per_frame(cur, next, [&](const zg_image *fa, const zg_image *fb) { return zg_warp(fa, fb, st.transform, st.m, &st.method, stream); });
-                    break;
-                }
-                }
-                cur = next;
-                if (i + 1 != n_steps) flip ^= 1;
-            }
-            i += take;
-        }
-    }
-    ping[0].reset(); // the first block first (an array's destructors run from its end): the order of frees decides which block a captured graph reuses
-    return rc;
+    for (const Shape &f : shape) ZG_REQUIRE(f.rows > 0 && f.cols > 0, ZG_ERR_INVALID_ARGUMENT, "pipeline: a step produces empty frames");
+    return run_steps(src_frames, n_frames, shape, steps, dst_frames, s);
 }
 
 int zg_batch_blur_resize(const void *src_frames, uint32_t n_frames, uint32_t rows, uint32_t cols, int pixel, float sigma,
@@ -300,58 +281,16 @@ int zg_batch_blur_resize(const void *src_frames, uint32_t n_frames, uint32_t row
     ZG_REQUIRE(sigma >= 0, ZG_ERR_INVALID_ARGUMENT, "batch: InvalidSigma (%g)", sigma);
     if (n_frames == 0 || rows == 0 || cols == 0 || out_rows == 0 || out_cols == 0) return ZG_OK;
     ZG_REQUIRE(src_frames && dst_frames, ZG_ERR_INVALID_ARGUMENT, "batch: null frame pointer");
-    hipStream_t s = as_stream(stream);
-    const size_t ps = pixel_size(pixel);
-    const size_t in_px = (size_t)rows * cols, out_px = (size_t)out_rows * out_cols;
-
-    // integer taps exactly as convolveSeparable derives them (convolution.zig:303-309) from gaussianBlur's f32 taps
-    std::vector<int32_t> taps;
-    if (sigma > 0 && pixel == ZG_PIXEL_RGBA_U8) {
-        if (const int rc = gaussian_taps_u8(sigma, taps)) return rc; // empty for kernels past 255 taps: they take the general per-frame path below
-        const int n = (int)taps.size();
-        const bool half = method->kind == ZG_INTERP_BILINEAR && rows == 2 * out_rows && cols == 2 * out_cols;
-        if (half && !taps.empty()) {
-            const StreamJob job{src_frames, dst_frames, n_frames, rows, cols, 4, (size_t)cols * 4, (size_t)out_cols * 4, in_px * 4, out_px * 4, true};
-            const int rcs = try_sep_stream(job, taps.data(), taps.data(), n, ZG_BORDER_MIRROR, s);
-            if (rcs >= 0) return rcs;
-            const Rgba8Batch b{src_frames, dst_frames, n_frames, rows, cols, cols, out_cols, in_px, out_px, true};
-            const int rc = try_sep_rgba8_batch(b, taps.data(), taps.data(), n, ZG_BORDER_MIRROR, s);
-            if (rc >= 0) return rc;
-        }
-    }
-
-    ScratchBlock block(s);
-    int rc = ZG_OK;
-    if (!taps.empty()) { // batched blur of every frame in one launch, then the reference's resize per frame
-        if ((rc = block.alloc((size_t)n_frames * in_px * ps))) return rc;
-        void *scratch = block.p;
-        const StreamJob job{src_frames, scratch, n_frames, rows, cols, 4, (size_t)cols * 4, (size_t)cols * 4, in_px * 4, in_px * 4, false};
-        rc = try_sep_stream(job, taps.data(), taps.data(), (int)taps.size(), ZG_BORDER_MIRROR, s);
-        if (rc < 0) {
-            const Rgba8Batch b{src_frames, scratch, n_frames, rows, cols, cols, cols, in_px, in_px, false};
-            rc = try_sep_rgba8_batch(b, taps.data(), taps.data(), (int)taps.size(), ZG_BORDER_MIRROR, s);
-        }
-        if (rc >= 0) {
-            for (uint32_t i = 0; i < n_frames && rc == ZG_OK; ++i) {
-                zg_image tmp{(char *)scratch + (size_t)i * in_px * ps, cols, rows, cols, pixel};
-                zg_image dst{(char *)dst_frames + (size_t)i * out_px * ps, out_cols, out_rows, out_cols, pixel};
-                rc = resize_impl(&tmp, &dst, method, s);
-            }
-            return rc;
-        }
-        block.reset(); // before the general path's allocation, which may take this block from the cache
-    }
-
-    // general path: two scratch frames so frame i+1's blur may start while frame i's resize still reads its scratch
-    if ((rc = block.alloc(2 * in_px * ps))) return rc;
-    for (uint32_t i = 0; i < n_frames && rc == ZG_OK; ++i) {
-        zg_image src{(char *)src_frames + (size_t)i * in_px * ps, cols, rows, cols, pixel};
-        zg_image tmp{block.p + (size_t)(i & 1) * in_px * ps, cols, rows, cols, pixel};
-        zg_image dst{(char *)dst_frames + (size_t)i * out_px * ps, out_cols, out_rows, out_cols, pixel};
-        rc = zg_gaussian_blur(&src, &tmp, sigma, stream);
-        if (rc == ZG_OK) rc = resize_impl(&tmp, &dst, method, s);
-    }
-    return rc;
+    zg_step steps[2] = {};
+    steps[0].kind = ZG_STEP_GAUSSIAN_BLUR;
+    steps[0].sigma = sigma;
+    steps[1].kind = ZG_STEP_RESIZE;
+    steps[1].out_rows = out_rows;
+    steps[1].out_cols = out_cols;
+    steps[1].method = *method;
+    std::vector<Shape> shape;
+    if (const int rc = shapes_of(Shape{rows, cols, pixel, ZG_CS_RGBA}, steps, 2, shape)) return rc; // the colour space: neither step reads it
+    return run_steps(src_frames, n_frames, shape, steps, dst_frames, as_stream(stream));
 }
 
 } // extern "C"

@@ -719,9 +719,12 @@ __global__ __launch_bounds__(256) void k_box_direct(DImg src, DImg dst, int radi
     P::store(dst.data, (size_t)r * dst.stride + (size_t)c, o);
 }
 
-// n equally shaped frames, src_frame / dst_frame bytes apart (n = 1: one image). Batches of frames go through the three kernels in groups whose SATs fit
+// Batches of frames go through the three kernels in groups whose SATs fit
 // a scratch block; one-plane images taller than 65 535 x 16 rows, and f32 sources, whose SAT kernels are per image, go frame by frame.
-static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, bool sharpen, hipStream_t s) {
+static int box_blur_frames_impl(const FrameBatch &b, uint32_t radius, bool sharpen, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
+    const size_t src_frame = b.src_frame, dst_frame = b.dst_frame;
     int rc;
     if ((rc = check_image(src, "src")) || (rc = check_image(dst, "dst"))) return rc;
     ZG_REQUIRE(src->rows == dst->rows && src->cols == dst->cols, ZG_ERR_DIMENSION_MISMATCH, "%s: %ux%u vs %ux%u", sharpen ? "sharpen" : "boxBlur",
@@ -754,7 +757,7 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
         }
     }
     // u8 planes and Rgba(u8), radius 1..3: the SAT stays in LDS (box_fused.hip)
-    if ((rc = try_box_fused(src, dst, n, src_frame, dst_frame, radius, sharpen, s)) >= 0) return rc;
+    if ((rc = try_box_fused(b, radius, sharpen, s)) >= 0) return rc;
     // sharpen reads the original pixel beside the SAT when it writes (k_box_mean): in place every lane reads the pixel it then writes, but into
     // a destination view that shares bytes with the source at another offset, lanes would read what others have written. The source is copied first.
     // One image only: a batch (n > 1) comes from the pipeline, whose source and destination frames are separate buffers; other callers of the
@@ -798,12 +801,12 @@ static int box_blur_frames_impl(const zg_image *src, const zg_image *dst, uint32
 }
 
 static int box_blur_impl(const zg_image *src, const zg_image *dst, uint32_t radius, bool sharpen, hipStream_t s) {
-    return box_blur_frames_impl(src, dst, 1, 0, 0, radius, sharpen, s);
+    return box_blur_frames_impl(FrameBatch{src, dst}, radius, sharpen, s);
 }
 
 // the pipeline's box-blur step over a batch (batch.hip)
-int box_blur_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, hipStream_t s) {
-    return box_blur_frames_impl(src, dst, n, src_frame, dst_frame, radius, false, s);
+int box_blur_frames(const FrameBatch &b, uint32_t radius, hipStream_t s) {
+    return box_blur_frames_impl(b, radius, false, s);
 }
 
 } // namespace zg

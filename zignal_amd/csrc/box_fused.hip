@@ -851,7 +851,10 @@ static bool box_fused_off() {
 }
 
 // -1: not this shape (the caller keeps the integral-image route)
-int try_box_fused(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, uint32_t radius, bool sharpen, hipStream_t s) {
+int try_box_fused(const FrameBatch &b, uint32_t radius, bool sharpen, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
+    const size_t src_frame = b.src_frame, dst_frame = b.dst_frame;
     if (box_fused_off()) return -1;
     if (src->pixel != ZG_PIXEL_U8 && src->pixel != ZG_PIXEL_RGBA_U8) return -1;
     if (radius < 1 || radius > (uint32_t)BF_MAX_R) return -1;

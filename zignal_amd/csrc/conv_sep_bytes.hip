@@ -231,14 +231,9 @@ int try_sep_bytes(const zg_image *src, const zg_image *dst, const int32_t *ix, c
     if ((src->cols * sp) % 16 || (src->stride * sp) % 16 || (dst->stride * sp) % 16 || ((uintptr_t)src->data & 15) || ((uintptr_t)dst->data & 15)) return -1;
     if (src->cols * sp < 256) return -1; // tiny images: the 1024-byte tile is mostly padding
     if ((uint64_t)src->cols * sp > 0x7fffffffu) return -1;
-    int64_t sx = 0, sy = 0;
-    for (int i = 0; i < nk; ++i) {
-        if (ix[i] < 0 || ix[i] > 255 || iy[i] < 0 || iy[i] > 255) return -1;
-        sx += ix[i];
-        sy += iy[i];
-    }
-    if (sx > 257 || sy > 257) return -1; // temp must fit u16: 255 * 257 = 65535
-    const bool clamp = sx * sy * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
+    TapSums sum;
+    if (!taps_pack_u16(ix, nk, iy, nk, sum)) return -1;
+    const bool clamp = sum.x * sum.y * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
     if (sp == 1) return dispatch_bytes<1>(src, dst, ix, iy, nk, clamp, border, s);
     if (sp == 3) return dispatch_bytes<3>(src, dst, ix, iy, nk, clamp, border, s);
     return dispatch_bytes<4>(src, dst, ix, iy, nk, clamp, border, s);

@@ -639,9 +639,9 @@ int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32
     if (src->cols % 16 || src->stride % 16 || ((uintptr_t)src->data & 15) || src->cols < 256 || (uint64_t)src->cols > 0x3fffffffu) return -1;
     if (level->rows == 0 || level->cols == 0 || level->rows > src->rows || level->cols > src->cols || src->rows < 2) return -1;
     if ((uint64_t)(src->rows + 16) * src->cols * 2 > 0x7fffffffull) return -1;
-    int64_t sum = 0;
-    for (int i = 0; i < nk; ++i) { if (taps[i] < 0 || taps[i] > 255) return -1; sum += taps[i]; }
-    if (sum > 257) return -1; // temp fits u16
+    TapSums both;
+    if (!taps_pack_u16(taps, nk, taps, nk, both)) return -1;
+    const int64_t sum = both.x;
     const bool wide = sum * sum * 255 + 32768 >= 256 * 65536; // a tap sum of 257: the biased accumulators of cols_strip_u8f<., true>
 
     const int row_bytes = (int)src->cols, half = nk / 2;
@@ -812,24 +812,24 @@ int try_pyramid_levels_u8(const zg_image *src, const zg_image *levels, const flo
 
 // Returns -1 when the preconditions do not hold (caller falls back to the general kernels).
 int try_sep_bytes2(const zg_image *src, const zg_image *dst, const int32_t *ix, int nkx, const int32_t *iy, int nky, int border, hipStream_t s) {
-    return try_sep_bytes2_frames(src, dst, 1, 0, 0, ix, nkx, iy, nky, border, s);
+    return try_sep_bytes2_frames(FrameBatch{src, dst}, ix, nkx, iy, nky, border, s);
 }
 
-// n frames of src's geometry, src_frame / dst_frame BYTES apart: the two passes run once per chunk of frames whose temp planes fit the
-// scratch budget, frame = blockIdx.y.
-int try_sep_bytes2_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, const int32_t *ix, int nkx,
-                          const int32_t *iy, int nky, int border, hipStream_t s) {
+// The two passes run once per chunk of frames whose temp planes fit the scratch budget, frame = blockIdx.y.
+int try_sep_bytes2_frames(const FrameBatch &b, const int32_t *ix, int nkx, const int32_t *iy, int nky, int border, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
+    const size_t src_frame = b.src_frame, dst_frame = b.dst_frame;
     if (src->pixel != ZG_PIXEL_U8 && src->pixel != ZG_PIXEL_RGB_U8 && src->pixel != ZG_PIXEL_RGBA_U8) return -1;
     if (nkx < 1 || nky < 1 || nkx > B2_NKMAX || nky > B2_NKMAX) return -1;
+    if (src->rows != dst->rows || src->cols != dst->cols) return -1; // no blur + 2:1 form here
     const size_t sp = pixel_size(src->pixel);
     if ((src->cols * sp) % 16 || (src->stride * sp) % 16 || (dst->stride * sp) % 16 || ((uintptr_t)src->data & 15) || ((uintptr_t)dst->data & 15)) return -1;
     if (src->cols * sp < 256 || (uint64_t)src->cols * sp > 0x3fffffffu) return -1;
-    int64_t sx = 0, sy = 0;
-    for (int i = 0; i < nkx; ++i) { if (ix[i] < 0 || ix[i] > 255) return -1; sx += ix[i]; }
-    for (int i = 0; i < nky; ++i) { if (iy[i] < 0 || iy[i] > 255) return -1; sy += iy[i]; }
-    if (sx > 257 || sy > 257) return -1; // temp must fit u16: 255 * 257 = 65535
-    const bool over = sx * sy * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
-    const bool wide = over && sx * sy * 255 + 32768 - (int64_t)U8F_BIAS <= 16777216; // ... and the biased f32 form still holds every sum (always: sums <= 257)
+    TapSums sum;
+    if (!taps_pack_u16(ix, nkx, iy, nky, sum)) return -1;
+    const bool over = sum.x * sum.y * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
+    const bool wide = over && sum.x * sum.y * 255 + 32768 - (int64_t)U8F_BIAS <= 16777216; // ... and the biased f32 form still holds every sum (always: sums <= 257)
     const bool clamp = over && !wide; // the integer column pass
 
     // row pass taps: tap j reads offset j - nkx / 2; the padded window starts at offset -hpad

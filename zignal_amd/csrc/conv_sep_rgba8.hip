@@ -223,39 +223,36 @@ __global__ __launch_bounds__(256) void k_sep_rgba8(DImg src, DImg dst, size_t sr
 }
 
 template <int NK, int RPT, bool CLAMP, bool DOWN2>
-static int launch_rgba8(const Rgba8Batch &b, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
+static int launch_rgba8(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
     TapsU8<NK> kx, ky;
     for (int i = 0; i < NK; ++i) { kx.k[i] = (uint32_t)ix[i]; ky.k[i] = (uint32_t)iy[i]; }
-    const int tiles_x = (int)ceil_div(b.cols, R8_TW), tiles_y = (int)ceil_div(b.rows, 4 * RPT);
+    const int tiles_x = (int)ceil_div(b.src->cols, R8_TW), tiles_y = (int)ceil_div(b.src->rows, 4 * RPT);
     const int tiles_per_frame = tiles_x * tiles_y;
-    const DImg src{(void *)b.src, b.src_stride, (int32_t)b.rows, (int32_t)b.cols};
-    const DImg dst{b.dst, b.dst_stride, (int32_t)(DOWN2 ? b.rows / 2 : b.rows), (int32_t)(DOWN2 ? b.cols / 2 : b.cols)};
-    hipLaunchKernelGGL((k_sep_rgba8<NK, RPT, true, CLAMP, DOWN2>), dim3((unsigned)(tiles_per_frame * b.n_frames)), dim3(256), 0, s,
-                       src, dst, b.src_frame_px, b.dst_frame_px, kx, ky, border, tiles_x, tiles_per_frame);
+    hipLaunchKernelGGL((k_sep_rgba8<NK, RPT, true, CLAMP, DOWN2>), dim3((unsigned)(tiles_per_frame * b.n)), dim3(256), 0, s,
+                       dimg(b.src), dimg(b.dst), b.src_frame / 4, b.dst_frame / 4, kx, ky, border, tiles_x, tiles_per_frame); // the kernel steps frames in pixels
     return launch_ok();
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the general kernels).
-int try_sep_rgba8_batch(const Rgba8Batch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s) {
+int try_sep_rgba8_batch(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s) {
+    const zg_image &src = *b.src, &dst = *b.dst;
+    if (src.pixel != ZG_PIXEL_RGBA_U8) return -1;
+    const bool down2 = src.rows == 2 * dst.rows && src.cols == 2 * dst.cols; // blur then 2:1 bilinear
+    if (!down2 && (src.rows != dst.rows || src.cols != dst.cols)) return -1;
     if (nk != 3 && nk != 5 && nk != 7 && nk != 9) return -1;
-    if (b.cols % 4 || b.src_stride % 4 || b.src_frame_px % 4 || ((uintptr_t)b.src & 15)) return -1;
-    if (b.down2) {
-        if (b.rows % 2 || b.cols % 4 || b.dst_stride % 2 || b.dst_frame_px % 2 || ((uintptr_t)b.dst & 7)) return -1;
+    if (src.cols % 4 || src.stride % 4 || b.src_frame % 16 || ((uintptr_t)src.data & 15)) return -1;
+    if (down2) {
+        if (src.rows % 2 || dst.stride % 2 || b.dst_frame % 8 || ((uintptr_t)dst.data & 7)) return -1;
     } else {
-        if (b.dst_stride % 4 || b.dst_frame_px % 4 || ((uintptr_t)b.dst & 15)) return -1;
+        if (dst.stride % 4 || b.dst_frame % 16 || ((uintptr_t)dst.data & 15)) return -1;
     }
-    if (b.cols < 64) return -1; // tiny images: the 256-wide tile is mostly padding
-    int64_t sx = 0, sy = 0;
-    for (int i = 0; i < nk; ++i) {
-        if (ix[i] < 0 || ix[i] > 255 || iy[i] < 0 || iy[i] > 255) return -1;
-        sx += ix[i];
-        sy += iy[i];
-    }
-    if (sx > 257 || sy > 257) return -1; // temp must fit u16: 255 * 257 = 65535
-    const bool clamp = sx * sy * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
+    if (src.cols < 64) return -1; // tiny images: the 256-wide tile is mostly padding
+    TapSums sum;
+    if (!taps_pack_u16(ix, nk, iy, nk, sum)) return -1;
+    const bool clamp = sum.x * sum.y * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
     // RPT 4 (21 KB of LDS, 7 workgroups / CU) measured best on MI355X: profiles/r01_sep_variant_sweep.txt
 #define ZG_R8(NK) case NK: \
-        if (b.down2) return clamp ? launch_rgba8<NK, (NK < 9 ? 8 : 4), true, true>(b, ix, iy, border, s) : launch_rgba8<NK, (NK < 9 ? 8 : 4), false, true>(b, ix, iy, border, s); \
+        if (down2) return clamp ? launch_rgba8<NK, (NK < 9 ? 8 : 4), true, true>(b, ix, iy, border, s) : launch_rgba8<NK, (NK < 9 ? 8 : 4), false, true>(b, ix, iy, border, s); \
         return clamp ? launch_rgba8<NK, 4, true, false>(b, ix, iy, border, s) : launch_rgba8<NK, 4, false, false>(b, ix, iy, border, s);
     switch (nk) { ZG_R8(3) ZG_R8(5) ZG_R8(7) ZG_R8(9) }
 #undef ZG_R8

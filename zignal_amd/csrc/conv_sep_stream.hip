@@ -405,8 +405,8 @@ __global__ __launch_bounds__(64) void k_sep_stream(StreamArgs a, TapsU8<NK> kx, 
 // help a kernel bound by instruction issue, fewer leave SIMDs idle — and taller strips for batches, where the 2H rows a strip
 // convolves for its upper neighbour are the only waste (measured on MI355X, profiles/r03_stream_kernel.txt: 4096^2 Rgba 32 rows,
 // 128 x 1080p 44). The count is then nudged so that a strip's row pairs fill whole blocks of the kernel's unrolled loop.
-static int stream_strip_rows(const StreamJob &j, uint32_t strips_x, int h, int d) {
-    const uint64_t all_rows = (uint64_t)j.rows * strips_x * j.n_frames;
+static int stream_strip_rows(const FrameBatch &b, uint32_t strips_x, int h, int d) {
+    const uint64_t all_rows = (uint64_t)b.src->rows * strips_x * b.n;
     uint64_t r = (all_rows + 2047) / 2048;
     r = std::min<uint64_t>(std::max<uint64_t>(r, 16), 44);
     int pairs = (int)((r + 1) / 2);
@@ -415,26 +415,27 @@ static int stream_strip_rows(const StreamJob &j, uint32_t strips_x, int h, int d
 }
 
 template <int SP, int NK, bool CLAMP, bool DOWN2>
-static int launch_stream(const StreamJob &j, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
+static int launch_stream(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
     TapsU8<NK> kx, ky;
     for (int i = 0; i < NK; ++i) { kx.k[i] = (uint32_t)ix[i]; ky.k[i] = (uint32_t)iy[i]; }
+    const uint32_t rows = b.src->rows;
     StreamArgs a;
-    a.src = (const uint8_t *)j.src;
-    a.dst = (uint8_t *)j.dst;
-    a.src_pitch = j.src_pitch; a.dst_pitch = j.dst_pitch;
-    a.src_frame = j.src_frame; a.dst_frame = j.dst_frame;
-    a.rows = (int32_t)j.rows;
-    a.row_bytes = (int32_t)(j.cols * (uint32_t)SP);
+    a.src = (const uint8_t *)b.src->data;
+    a.dst = (uint8_t *)b.dst->data;
+    a.src_pitch = b.src->stride * SP; a.dst_pitch = b.dst->stride * SP;
+    a.src_frame = b.src_frame; a.dst_frame = b.dst_frame;
+    a.rows = (int32_t)rows;
+    a.row_bytes = (int32_t)(b.src->cols * (uint32_t)SP);
     a.strips_x = (int32_t)ceil_div((unsigned)a.row_bytes, 1024u);
-    a.strip_rows = stream_strip_rows(j, (uint32_t)a.strips_x, NK / 2, NK / 2 + 1);
-    a.strips_y = (int32_t)ceil_div(j.rows, (unsigned)a.strip_rows);
+    a.strip_rows = stream_strip_rows(b, (uint32_t)a.strips_x, NK / 2, NK / 2 + 1);
+    a.strips_y = (int32_t)ceil_div(rows, (unsigned)a.strip_rows);
     a.border = border;
-    const uint64_t sspan = (uint64_t)(j.rows - 1) * j.src_pitch + (uint64_t)a.row_bytes;
-    const uint64_t dspan = j.down2 ? (uint64_t)(j.rows / 2 - 1) * j.dst_pitch + (uint64_t)(a.row_bytes / 2) : (uint64_t)(j.rows - 1) * j.dst_pitch + (uint64_t)a.row_bytes;
+    const uint64_t sspan = (uint64_t)(rows - 1) * a.src_pitch + (uint64_t)a.row_bytes;
+    const uint64_t dspan = DOWN2 ? (uint64_t)(rows / 2 - 1) * a.dst_pitch + (uint64_t)(a.row_bytes / 2) : (uint64_t)(rows - 1) * a.dst_pitch + (uint64_t)a.row_bytes;
     a.fast_ok = sspan <= 0xffffffffu && dspan <= 0xffffffffu;
     a.src_span = (uint32_t)sspan;
     a.dst_span = (uint32_t)dspan;
-    const uint64_t items = (uint64_t)a.strips_x * a.strips_y * j.n_frames;
+    const uint64_t items = (uint64_t)a.strips_x * a.strips_y * b.n;
     if (items > 0x7fffffffu) return -1;
     // row taps symmetric with unit ends: the folded row pass (the CLAMP instantiations — tap sums past 256 — keep the plain one)
     static const bool no_fold = getenv("ZIGNAL_HIP_STREAM_NO_FOLD") != nullptr; // A/B hook of round 5, read once
@@ -451,34 +452,33 @@ static int launch_stream(const StreamJob &j, const int32_t *ix, const int32_t *i
 }
 
 // Returns -1 when the preconditions do not hold (caller falls back to the tiled kernels).
-int try_sep_stream(const StreamJob &j, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s) {
-    if (j.sp != 1 && j.sp != 3 && j.sp != 4) return -1;
+int try_sep_stream(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s) {
+    const zg_image &src = *b.src, &dst = *b.dst;
+    if (src.pixel != ZG_PIXEL_U8 && src.pixel != ZG_PIXEL_RGB_U8 && src.pixel != ZG_PIXEL_RGBA_U8) return -1;
+    const bool down2 = src.rows == 2 * dst.rows && src.cols == 2 * dst.cols; // blur then 2:1 bilinear
+    if (!down2 && (src.rows != dst.rows || src.cols != dst.cols)) return -1;
+    const size_t sp = pixel_size(src.pixel), src_pitch = src.stride * sp, dst_pitch = dst.stride * sp; // bytes per pixel, bytes between rows
     // a single grey plane is the one case the LDS-tiled kernel still wins (10.4 against 11.9 us at 4096^2): 16 pixels per lane leave
     // it little halo to re-convolve, and a 4 KiB-wide row gives this kernel only four strips across
-    if (j.sp == 1 && j.n_frames == 1) return -1;
+    if (sp == 1 && b.n == 1) return -1;
     if (nk != 3 && nk != 5 && nk != 7 && nk != 9) return -1;
-    if ((nk / 2 + 1) * j.sp > 16) return -1;
-    const uint64_t rb = (uint64_t)j.cols * (uint64_t)j.sp;
-    if (rb % 16 || j.src_pitch % 16 || j.src_frame % 16 || ((uintptr_t)j.src & 15)) return -1;
+    if ((nk / 2 + 1) * sp > 16) return -1;
+    const uint64_t rb = (uint64_t)src.cols * sp;
+    if (rb % 16 || src_pitch % 16 || b.src_frame % 16 || ((uintptr_t)src.data & 15)) return -1;
     if (rb % 1024 == 16) return -1; // the last strip would be one lane wide: that lane is first and last at once
-    if (j.cols < 64 || j.rows < 16 || rb > 0x3fffffffu || j.src_pitch > 0x7fffffffu || j.dst_pitch > 0x7fffffffu) return -1;
-    if (j.down2) {
-        if (j.sp != 4 || j.rows % 2 || rb % 32 || j.dst_pitch % 8 || j.dst_frame % 8 || ((uintptr_t)j.dst & 7)) return -1;
+    if (src.cols < 64 || src.rows < 16 || rb > 0x3fffffffu || src_pitch > 0x7fffffffu || dst_pitch > 0x7fffffffu) return -1;
+    if (down2) {
+        if (sp != 4 || src.rows % 2 || rb % 32 || dst_pitch % 8 || b.dst_frame % 8 || ((uintptr_t)dst.data & 7)) return -1;
     } else {
-        if (j.dst_pitch % 16 || j.dst_frame % 16 || ((uintptr_t)j.dst & 15)) return -1;
+        if (dst_pitch % 16 || b.dst_frame % 16 || ((uintptr_t)dst.data & 15)) return -1;
     }
-    int64_t sx = 0, sy = 0;
-    for (int i = 0; i < nk; ++i) {
-        if (ix[i] < 0 || ix[i] > 255 || iy[i] < 0 || iy[i] > 255) return -1;
-        sx += ix[i];
-        sy += iy[i];
-    }
-    if (sx > 257 || sy > 257) return -1; // temp must fit u16: 255 * 257 = 65535
-    const bool clamp = sx * sy * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
+    TapSums sum;
+    if (!taps_pack_u16(ix, nk, iy, nk, sum)) return -1;
+    const bool clamp = sum.x * sum.y * 255 + 32768 >= 256 * 65536; // only then can (acc >> 16) exceed 255
 #define ZG_ST(SP, NK) \
-    if (j.sp == SP && nk == NK) { \
-        if constexpr (SP == 4) { if (j.down2) return clamp ? launch_stream<SP, NK, true, true>(j, ix, iy, border, s) : launch_stream<SP, NK, false, true>(j, ix, iy, border, s); } \
-        return clamp ? launch_stream<SP, NK, true, false>(j, ix, iy, border, s) : launch_stream<SP, NK, false, false>(j, ix, iy, border, s); \
+    if (sp == SP && nk == NK) { \
+        if constexpr (SP == 4) { if (down2) return clamp ? launch_stream<SP, NK, true, true>(b, ix, iy, border, s) : launch_stream<SP, NK, false, true>(b, ix, iy, border, s); } \
+        return clamp ? launch_stream<SP, NK, true, false>(b, ix, iy, border, s) : launch_stream<SP, NK, false, false>(b, ix, iy, border, s); \
     }
     ZG_ST(1, 3) ZG_ST(1, 5) ZG_ST(1, 7) ZG_ST(1, 9)
     ZG_ST(3, 3) ZG_ST(3, 5) ZG_ST(3, 7) ZG_ST(3, 9)

@@ -571,9 +571,7 @@ static int conv_separable_impl(const zg_image *src, const zg_image *dst, const f
                           max_temp * say < (int64_t)INT32_MAX - 65536;
         p.mode = fits ? MODE_I24 : MODE_I64;
         if (p.nkx == p.nky) { // small non-negative taps: packed-u16 arithmetic on the row as a byte stream, 16 bytes / lane
-            const size_t sp = pixel_size(src->pixel);
-            const StreamJob job{src->data, dst->data, 1, src->rows, src->cols, (int)sp, src->stride * sp, dst->stride * sp, 0, 0, false};
-            const int rcs = try_sep_stream(job, p.ix.data(), p.iy.data(), p.nkx, border, s); // one wave per column strip, no LDS
+            const int rcs = try_sep_stream(FrameBatch{src, dst}, p.ix.data(), p.iy.data(), p.nkx, border, s); // one wave per column strip, no LDS
             if (rcs >= 0) return rcs;
             const int rcb = try_sep_bytes(src, dst, p.ix.data(), p.iy.data(), p.nkx, border, s);
             if (rcb >= 0) return rcb;
@@ -656,6 +654,13 @@ int gaussian_taps_i32(float sigma, int32_t *taps, int capacity, GaussianTapsI32 
     }
     out.z = zero_ends(taps, out.n);
     return ZG_OK;
+}
+
+bool taps_pack_u16(const int32_t *ix, int nkx, const int32_t *iy, int nky, TapSums &sums) {
+    sums = TapSums{};
+    for (int i = 0; i < nkx; ++i) { if (ix[i] < 0 || ix[i] > 255) return false; sums.x += ix[i]; }
+    for (int i = 0; i < nky; ++i) { if (iy[i] < 0 || iy[i] > 255) return false; sums.y += iy[i]; }
+    return sums.x <= 257 && sums.y <= 257;
 }
 
 } // namespace zg

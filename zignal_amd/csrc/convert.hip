@@ -505,8 +505,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_resize_bilinear_rgba8_to_lab(DIm
 }
 
 // [resize(.bilinear), convert(Oklab | Xyz f32)] of n Rgba(u8) frames in one launch; -1 when the fused kernel does not apply.
-int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int dst_space, uint32_t n, size_t src_frame, size_t dst_frame, const float *srgb_lut,
-                                hipStream_t s) {
+int resize_convert_rgba8_frames(const FrameBatch &b, int dst_space, const float *srgb_lut, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
     const bool fused = src->pixel == ZG_PIXEL_RGBA_U8 && dst->pixel == ZG_PIXEL_RGB_F32 && (dst_space == ZG_CS_OKLAB || dst_space == ZG_CS_XYZ) && src->rows > 0 &&
                        src->cols >= 2 && dst->rows > 0 && dst->cols > 0 && n > 0 && !(src->rows == dst->rows && src->cols == dst->cols);
     if (!fused) return -1;
@@ -523,7 +524,7 @@ int resize_convert_rgba8_frames(const zg_image *src, const zg_image *dst, int ds
     bool plain_table = false;
     if (int rc = device_srgb_lut(srgb_lut, s, &lut_dev, &owned, &plain_table)) return rc;
     const float ratio_x = (float)src->cols / (float)dst->cols, ratio_y = (float)src->rows / (float)dst->rows;
-    const FrameSpan fr{src_frame, dst_frame};
+    const FrameSpan fr = b.span();
     const int mode = dst_space != ZG_CS_OKLAB ? 0 : (plain_table ? 2 : 1);
 #define ZG_RL(MODE) \
     if (mode == MODE) { \
@@ -543,7 +544,7 @@ static int resize_convert_impl(const zg_image *src, int src_space, const zg_imag
     ZG_REQUIRE(src_space >= ZG_CS_GRAY && src_space <= ZG_CS_XYB && dst_space >= ZG_CS_GRAY && dst_space <= ZG_CS_XYB, ZG_ERR_INVALID_ARGUMENT, "resize + convert: invalid colour space");
     if (dst->rows == 0 || dst->cols == 0) return ZG_OK;
     if (src_space == ZG_CS_RGBA && method->kind == ZG_INTERP_BILINEAR) {
-        const int rcf = resize_convert_rgba8_frames(src, dst, dst_space, 1, 0, 0, srgb_lut, s);
+        const int rcf = resize_convert_rgba8_frames(FrameBatch{src, dst}, dst_space, srgb_lut, s);
         if (rcf >= 0) return rcf;
     }
     // every other combination: the two steps as they are, through a resized image that lives in scratch for the call

@@ -101,7 +101,10 @@ __global__ __launch_bounds__(256) void k_sobel(DImg src, DImg dst, int tiles_x, 
     }
 }
 
-static int sobel_impl(const zg_image *src, const zg_image *dst, hipStream_t s, uint32_t n = 1, size_t src_frame = 0, size_t dst_frame = 0) {
+// Image.sobel of n equally shaped frames in one launch (-1: too many frames for one grid)
+int sobel_frames(const FrameBatch &b, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
     int rc;
     if ((rc = check_image(src, "src")) || (rc = check_image(dst, "dst"))) return rc;
     ZG_REQUIRE(src->rows == dst->rows && src->cols == dst->cols, ZG_ERR_DIMENSION_MISMATCH, "sobel: %ux%u vs %ux%u",
@@ -119,19 +122,15 @@ static int sobel_impl(const zg_image *src, const zg_image *dst, hipStream_t s, u
         if ((rc = copy_impl(src, &copy, s))) return rc;
         src = &copy;
     }
-    if (const int rcs = try_sobel_stream(src, dst, n, src_frame, dst_frame, s); rcs >= 0) return rcs; // u8 / Rgba(u8): one wave per column strip
+    if (const int rcs = try_sobel_stream(FrameBatch{src, dst, n, b.src_frame, b.dst_frame}, s); rcs >= 0) return rcs; // u8 / Rgba(u8): one wave per column strip
     const int tiles_x = (int)ceil_div(src->cols, 64), tiles_y = (int)ceil_div(src->rows, 16);
     if (n > MAX_FRAMES_PER_LAUNCH) return -1; // the caller goes frame by frame
-    const FrameSpan fr{src_frame, dst_frame};
+    const FrameSpan fr = b.span();
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         hipLaunchKernelGGL((k_sobel<PIX>), dim3((unsigned)(tiles_x * tiles_y), n), dim3(256), 0, s, dimg(src), dimg(dst), tiles_x, fr);
         return launch_ok();
     });
-}
-// Image.sobel of n equally shaped frames in one launch (-1: too many frames for one grid)
-int sobel_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
-    return sobel_impl(src, dst, s, n, src_frame, dst_frame);
 }
 
 
@@ -660,10 +659,10 @@ using namespace zg;
 
 extern "C" {
 
-int zg_sobel(const zg_image *src, const zg_image *dst, zg_stream stream) { return sobel_impl(src, dst, as_stream(stream)); }
+int zg_sobel(const zg_image *src, const zg_image *dst, zg_stream stream) { return sobel_frames(FrameBatch{src, dst}, as_stream(stream)); }
 
 int zg_sobel_host(const zg_image *src, const zg_image *dst) {
-    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return sobel_impl(a, b, nullptr); });
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return sobel_frames(FrameBatch{a, b}, nullptr); });
 }
 
 int zg_canny(const zg_image *src, const zg_image *dst, float sigma, float low_threshold, float high_threshold, zg_stream stream) {

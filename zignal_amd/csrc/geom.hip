@@ -150,18 +150,15 @@ static int check_method(const zg_method *method) {
     return ZG_OK;
 }
 
-struct FrameBatch { // n frames src_frame / dst_frame bytes apart (defaults: the one image)
-    uint32_t n = 1;
-    size_t src_frame = 0, dst_frame = 0;
-};
 template <int PIX, int KIND>
-static int launch_geom_k(const zg_image *src, const zg_image *dst, const GeomParams &g, const MethodArg &m, int border, const FrameBatch &fb, hipStream_t s) {
+static int launch_geom_k(const FrameBatch &fb, const GeomParams &g, const MethodArg &m, int border, hipStream_t s) {
+    const zg_image *src = fb.src, *dst = fb.dst;
     const int tiles_x = (int)ceil_div(dst->cols, 64), tiles_y = (int)ceil_div(dst->rows, 4);
     const uint64_t tiles = (uint64_t)tiles_x * tiles_y;
     ZG_REQUIRE(tiles <= 0x7fffffffu, ZG_ERR_INVALID_ARGUMENT, "too many tiles in one launch (%llu)", (unsigned long long)tiles);
     if (fb.n > MAX_FRAMES_PER_LAUNCH) return -1; // the caller goes frame by frame
     const dim3 grid((unsigned)tiles, fb.n);
-    const FrameSpan fr{fb.src_frame, fb.dst_frame};
+    const FrameSpan fr = fb.span();
     constexpr bool CAN_STAGE = PIX == ZG_PIXEL_RGBA_F32 && (KIND == ZG_INTERP_BICUBIC || KIND == ZG_INTERP_CATMULL_ROM || KIND == ZG_INTERP_MITCHELL);
     if constexpr (CAN_STAGE) {
         // for every map: where a wave cannot stage, this kernel's row-at-a-time gather (seven waves per SIMD) still beats the sixteen gathers
@@ -173,7 +170,8 @@ static int launch_geom_k(const zg_image *src, const zg_image *dst, const GeomPar
     return launch_ok();
 }
 
-static int launch_geom(const zg_image *src, const zg_image *dst, const GeomParams &g, const zg_method *method, int border, hipStream_t s, const FrameBatch &fb = FrameBatch{}) {
+static int launch_geom(const FrameBatch &fb, const GeomParams &g, const zg_method *method, int border, hipStream_t s) {
+    const zg_image *src = fb.src, *dst = fb.dst;
     int rc;
     if ((rc = check_method(method))) return rc;
     ZG_REQUIRE(border >= ZG_BORDER_ZERO && border <= ZG_BORDER_WRAP, ZG_ERR_INVALID_ARGUMENT, "invalid border %d", border);
@@ -186,12 +184,12 @@ static int launch_geom(const zg_image *src, const zg_image *dst, const GeomParam
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         switch (method->kind) {
-        case ZG_INTERP_NEAREST: return launch_geom_k<PIX, ZG_INTERP_NEAREST>(src, dst, gp, m, border, fb, s);
-        case ZG_INTERP_BILINEAR: return launch_geom_k<PIX, ZG_INTERP_BILINEAR>(src, dst, gp, m, border, fb, s);
-        case ZG_INTERP_BICUBIC: return launch_geom_k<PIX, ZG_INTERP_BICUBIC>(src, dst, gp, m, border, fb, s);
-        case ZG_INTERP_CATMULL_ROM: return launch_geom_k<PIX, ZG_INTERP_CATMULL_ROM>(src, dst, gp, m, border, fb, s);
-        case ZG_INTERP_MITCHELL: return launch_geom_k<PIX, ZG_INTERP_MITCHELL>(src, dst, gp, m, border, fb, s);
-        default: return launch_geom_k<PIX, ZG_INTERP_LANCZOS>(src, dst, gp, m, border, fb, s);
+        case ZG_INTERP_NEAREST: return launch_geom_k<PIX, ZG_INTERP_NEAREST>(fb, gp, m, border, s);
+        case ZG_INTERP_BILINEAR: return launch_geom_k<PIX, ZG_INTERP_BILINEAR>(fb, gp, m, border, s);
+        case ZG_INTERP_BICUBIC: return launch_geom_k<PIX, ZG_INTERP_BICUBIC>(fb, gp, m, border, s);
+        case ZG_INTERP_CATMULL_ROM: return launch_geom_k<PIX, ZG_INTERP_CATMULL_ROM>(fb, gp, m, border, s);
+        case ZG_INTERP_MITCHELL: return launch_geom_k<PIX, ZG_INTERP_MITCHELL>(fb, gp, m, border, s);
+        default: return launch_geom_k<PIX, ZG_INTERP_LANCZOS>(fb, gp, m, border, s);
         }
     });
 }
@@ -404,13 +402,15 @@ __global__ __launch_bounds__(256) void k_resize_bilinear_u8_rows(DImg src, DImg 
 }
 
 // n equally shaped u8 planes (n = 1: the one image); sizes the caller has already checked
-static int launch_resize_bilinear_u8(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
+static int launch_resize_bilinear_u8(const FrameBatch &b, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
     const int tiles_x = (int)ceil_div(dst->cols, 256), tiles_y = (int)ceil_div(dst->rows, 4);
     const uint64_t tiles = (uint64_t)tiles_x * tiles_y;
     ZG_REQUIRE(tiles <= 0x7fffffffu, ZG_ERR_INVALID_ARGUMENT, "too many tiles in one launch (%llu)", (unsigned long long)tiles);
     if (n > MAX_FRAMES_PER_LAUNCH) return -1; // the caller goes frame by frame
-    const FrameSpan fr{src_frame, dst_frame};
-    const int dword_rows = ((uintptr_t)dst->data % 4 == 0 && dst->stride % 4 == 0 && dst_frame % 4 == 0) ? 1 : 0;
+    const FrameSpan fr = b.span();
+    const int dword_rows = ((uintptr_t)dst->data % 4 == 0 && dst->stride % 4 == 0 && b.dst_frame % 4 == 0) ? 1 : 0;
     const float rx = (float)src->cols / (float)dst->cols;
     static const int rows_form = getenv("ZIGNAL_HIP_RESIZE_U8_ROWS") ? atoi(getenv("ZIGNAL_HIP_RESIZE_U8_ROWS")) : 2; // A/B hook of round 5: 0 = the one-row kernel; 4096^2 -> 3413^2: 21.3 / 18.2 / 20.4 us for 0 / 2 / 4 rows
     if (rows_form > 0 && rx < 2.0f && src->cols >= 8) { // taps computed once for several rows, one 8-byte load per source row and lane
@@ -436,31 +436,30 @@ int resize_impl(const zg_image *src, const zg_image *dst, const zg_method *metho
     if (src->rows == dst->rows && src->cols == dst->cols) return copy_impl(src, dst, s); // :91-108
     const bool is_rgb_u8 = src->pixel == ZG_PIXEL_RGB_U8 || src->pixel == ZG_PIXEL_RGBA_U8; // meta.isRgb(T)
     if (is_rgb_u8 && src->rows > 0 && src->cols > 0) return resize_planes_impl(src, dst, method, s);
-    if (resize_u8_plane_applies(src, dst, method)) return launch_resize_bilinear_u8(src, dst, 1, 0, 0, s);
+    if (resize_u8_plane_applies(src, dst, method)) return launch_resize_bilinear_u8(FrameBatch{src, dst}, s);
     GeomParams g{};
     g.mode = GEOM_RESIZE;
     g.p[0] = (float)src->cols / (float)dst->cols;
     g.p[1] = (float)src->rows / (float)dst->rows;
-    return launch_geom(src, dst, g, method, ZG_BORDER_MIRROR, s);
+    return launch_geom(FrameBatch{src, dst}, g, method, ZG_BORDER_MIRROR, s);
 }
 
 // resize of n equally shaped frames in one launch where the path is a single kernel with a frame index (the generic interpolators of every
 // type, and the Rgb(u8) / Rgba(u8) plane resizers); -1 otherwise (zg_batch_pipeline then goes frame by frame).
-int resize_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
+int resize_frames(const FrameBatch &b, const zg_method *method, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
     int rc;
     if ((rc = check_pair(src, dst, "resize")) || (rc = check_method(method))) return rc;
-    if (n == 0 || dst->rows == 0 || dst->cols == 0 || src->rows == 0 || src->cols == 0) return -1;
+    if (b.n == 0 || dst->rows == 0 || dst->cols == 0 || src->rows == 0 || src->cols == 0) return -1;
     if (src->rows == dst->rows && src->cols == dst->cols) return -1; // a copy per frame
     const bool is_rgb_u8 = src->pixel == ZG_PIXEL_RGB_U8 || src->pixel == ZG_PIXEL_RGBA_U8;
-    if (is_rgb_u8) return resize_planes_frames(src, dst, method, n, src_frame, dst_frame, s); // every method: the frame is the grid's y
-    if (resize_u8_plane_applies(src, dst, method)) return launch_resize_bilinear_u8(src, dst, n, src_frame, dst_frame, s);
+    if (is_rgb_u8) return resize_planes_frames(b, method, s); // every method: the frame is the grid's y
+    if (resize_u8_plane_applies(src, dst, method)) return launch_resize_bilinear_u8(b, s);
     GeomParams g{};
     g.mode = GEOM_RESIZE;
     g.p[0] = (float)src->cols / (float)dst->cols;
     g.p[1] = (float)src->rows / (float)dst->rows;
-    FrameBatch fb;
-    fb.n = n; fb.src_frame = src_frame; fb.dst_frame = dst_frame;
-    return launch_geom(src, dst, g, method, ZG_BORDER_MIRROR, s, fb);
+    return launch_geom(b, g, method, ZG_BORDER_MIRROR, s);
 }
 
 // Image(Rgb(u8) / Rgba(u8)).resize(.lanczos) with the caller's plane weights (channel_ops.zig:438-493)
@@ -517,9 +516,10 @@ static int letterbox_impl(const zg_image *src, const zg_image *dst, const zg_met
 }
 
 // ---- warp (transforms.zig:522-531) ------------------------------------------------------------------
-static int warp_impl(const zg_image *src, const zg_image *dst, int kind, const float *mat, const zg_method *method, hipStream_t s, const FrameBatch &fb = FrameBatch{}) {
+// (the same warp applied to every frame of a batch in one launch)
+int warp_frames(const FrameBatch &fb, int kind, const float *mat, const zg_method *method, hipStream_t s) {
     int rc;
-    if ((rc = check_pair(src, dst, "warp"))) return rc;
+    if ((rc = check_pair(fb.src, fb.dst, "warp"))) return rc;
     ZG_REQUIRE(mat != nullptr, ZG_ERR_INVALID_ARGUMENT, "warp: null transform coefficients");
     ZG_REQUIRE(kind >= ZG_TRANSFORM_SIMILARITY && kind <= ZG_TRANSFORM_PROJECTIVE, ZG_ERR_INVALID_ARGUMENT, "warp: invalid transform kind %d", kind);
     GeomParams g{};
@@ -530,13 +530,7 @@ static int warp_impl(const zg_image *src, const zg_image *dst, int kind, const f
         g.mode = GEOM_AFFINE;
         for (int i = 0; i < 6; ++i) g.p[i] = mat[i];
     }
-    return launch_geom(src, dst, g, method, ZG_BORDER_MIRROR, s, fb);
-}
-// the same warp applied to n equally shaped frames in one launch
-int warp_frames(const zg_image *src, const zg_image *dst, int kind, const float *mat, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
-    FrameBatch fb;
-    fb.n = n; fb.src_frame = src_frame; fb.dst_frame = dst_frame;
-    return warp_impl(src, dst, kind, mat, method, s, fb);
+    return launch_geom(fb, g, method, ZG_BORDER_MIRROR, s);
 }
 
 // ---- rotate (transforms.zig:112-212, :385-462) -----------------------------------------------------
@@ -602,7 +596,7 @@ static int rotate_into_impl(const zg_image *src, const zg_image *dst, float angl
     GeomParams g{};
     g.mode = GEOM_ROTATE;
     g.p[0] = cos_a; g.p[1] = sin_a; g.p[2] = cx + offset_x; g.p[3] = cy + offset_y; g.p[4] = cx; g.p[5] = cy;
-    return launch_geom(src, dst, g, method, border, s);
+    return launch_geom(FrameBatch{src, dst}, g, method, border, s);
 }
 
 // ---- extract / crop (transforms.zig:216-282, copyRect :465-518) ---------------------------------------
@@ -646,7 +640,7 @@ static int extract_impl(const zg_image *src, const zg_image *dst, const float re
     g.p[6] = (rect[0] + rect[2]) * 0.5f; g.p[7] = (rect[1] + rect[3]) * 0.5f;
     g.p[8] = fcols - 1; g.p[9] = frows - 1;
     g.p[10] = dst->cols == 1 ? 1.0f : 0.0f; g.p[11] = dst->rows == 1 ? 1.0f : 0.0f;
-    return launch_geom(src, dst, g, method, border, s);
+    return launch_geom(FrameBatch{src, dst}, g, method, border, s);
 }
 
 // ---- insert (transforms.zig:293-378) -------------------------------------------------------------------
@@ -836,10 +830,10 @@ int zg_letterbox_host(const zg_image *src, const zg_image *dst, const zg_method 
 }
 
 int zg_warp(const zg_image *src, const zg_image *dst, int kind, const float *m, const zg_method *method, zg_stream stream) {
-    return warp_impl(src, dst, kind, m, method, as_stream(stream));
+    return warp_frames(FrameBatch{src, dst}, kind, m, method, as_stream(stream));
 }
 int zg_warp_host(const zg_image *src, const zg_image *dst, int kind, const float *m, const zg_method *method) {
-    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return warp_impl(a, b, kind, m, method, nullptr); });
+    return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return warp_frames(FrameBatch{a, b}, kind, m, method, nullptr); });
 }
 
 int zg_rotate_into(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a,

@@ -127,8 +127,10 @@ static int motion_check(const zg_image *src, const zg_image *dst, const char *wh
 
 // n equally shaped frames src_frame / dst_frame bytes apart (n = 1: one image). The gather kernels take the batch in gridDim.z (up to 65 535 frames
 // per launch); the axis-aligned linear case is the separable convolution, frame by frame.
-static int motion_linear_frames_impl(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float cos_a, float sin_a, uint32_t distance,
-                                     zg_stream stream) {
+static int motion_linear_frames_impl(const FrameBatch &b, float cos_a, float sin_a, uint32_t distance, zg_stream stream) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
+    const size_t src_frame = b.src_frame, dst_frame = b.dst_frame;
     hipStream_t s = as_stream(stream);
     int rc;
     if ((rc = motion_check(src, dst, "motionBlur.linear"))) return rc;
@@ -149,7 +151,7 @@ static int motion_linear_frames_impl(const zg_image *src, const zg_image *dst, u
         return ZG_OK;
     }
     if (src->rows == 0 || src->cols == 0 || n == 0) return ZG_OK;
-    const FrameSpan fr{src_frame, dst_frame};
+    const FrameSpan fr = b.span();
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {
@@ -161,8 +163,10 @@ static int motion_linear_frames_impl(const zg_image *src, const zg_image *dst, u
     });
 }
 
-static int motion_radial_frames_impl(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float center_x, float center_y, float strength,
-                                     int spin, zg_stream stream) {
+static int motion_radial_frames_impl(const FrameBatch &b, float center_x, float center_y, float strength, int spin, zg_stream stream) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
+    const size_t src_frame = b.src_frame, dst_frame = b.dst_frame;
     hipStream_t s = as_stream(stream);
     int rc;
     if ((rc = motion_check(src, dst, "motionBlur.radial"))) return rc;
@@ -179,7 +183,7 @@ static int motion_radial_frames_impl(const zg_image *src, const zg_image *dst, u
     const float cx = center_x * (float)(src->cols - 1), cy = center_y * (float)(src->rows - 1);
     const float clamped = std::fmax(0.0f, std::fmin(1.0f, strength));
     const int num_samples = 8 + (int)std::trunc(clamped * 24.0f);
-    const FrameSpan fr{src_frame, dst_frame};
+    const FrameSpan fr = b.span();
     return dispatch_pixel(src->pixel, [&](auto tag) -> int {
         constexpr int PIX = decltype(tag)::value;
         for (uint32_t f0 = 0; f0 < n; f0 += 65535u) {
@@ -194,19 +198,18 @@ static int motion_radial_frames_impl(const zg_image *src, const zg_image *dst, u
 
 static int motion_linear_impl(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a, uint32_t distance, zg_stream stream) {
     (void)angle;
-    return motion_linear_frames_impl(src, dst, 1, 0, 0, cos_a, sin_a, distance, stream);
+    return motion_linear_frames_impl(FrameBatch{src, dst}, cos_a, sin_a, distance, stream);
 }
 static int motion_radial_impl(const zg_image *src, const zg_image *dst, float center_x, float center_y, float strength, int spin, zg_stream stream) {
-    return motion_radial_frames_impl(src, dst, 1, 0, 0, center_x, center_y, strength, spin, stream);
+    return motion_radial_frames_impl(FrameBatch{src, dst}, center_x, center_y, strength, spin, stream);
 }
 
 // the pipeline's motion-blur step over a batch (batch.hip)
-int motion_linear_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float cos_a, float sin_a, uint32_t distance, hipStream_t s) {
-    return motion_linear_frames_impl(src, dst, n, src_frame, dst_frame, cos_a, sin_a, distance, (zg_stream)s);
+int motion_linear_frames(const FrameBatch &b, float cos_a, float sin_a, uint32_t distance, hipStream_t s) {
+    return motion_linear_frames_impl(b, cos_a, sin_a, distance, (zg_stream)s);
 }
-int motion_radial_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, float center_x, float center_y, float strength, int spin,
-                         hipStream_t s) {
-    return motion_radial_frames_impl(src, dst, n, src_frame, dst_frame, center_x, center_y, strength, spin, (zg_stream)s);
+int motion_radial_frames(const FrameBatch &b, float center_x, float center_y, float strength, int spin, hipStream_t s) {
+    return motion_radial_frames_impl(b, center_x, center_y, strength, spin, (zg_stream)s);
 }
 
 } // namespace zg

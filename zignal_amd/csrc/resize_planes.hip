@@ -397,7 +397,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_resize_bilinear_rgba8(DImg src, 
 }
 
 // Image(Rgba(u8)).resize(.bilinear) of n frames in one launch; -1 when the fast kernel does not apply (the caller goes frame by frame).
-int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
+int resize_bilinear_rgba8_frames(const FrameBatch &b, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
     if (src->pixel != ZG_PIXEL_RGBA_U8 || dst->pixel != ZG_PIXEL_RGBA_U8 || src->cols < 2 || src->rows == 0 || dst->rows == 0 || dst->cols == 0 || n == 0) return -1;
     if (src->rows == dst->rows && src->cols == dst->cols) return -1; // equal sizes are a copy (interpolation.zig:100-108)
     // Launch form (profiles/r05_experiments.txt; tools/exp/copy_floor.hip is why): strong reductions read a few bytes per output pixel, and there
@@ -411,12 +413,12 @@ int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint3
     const int waves = form == 0 ? 4 : 1, rpw = form == 0 ? 1 : form;
     const int tiles_x = (int)ceil_div(dst->cols, 64), tiles_y = (int)ceil_div(dst->rows, (unsigned)(waves * rpw));
     const float ratio_x = (float)src->cols / (float)dst->cols, ratio_y = (float)src->rows / (float)dst->rows;
-    const bool x4 = ratio_x <= 1.5f && dst->cols % 4 == 0 && dst->stride % 4 == 0 && ((uintptr_t)dst->data & 15) == 0 && dst_frame % 16 == 0;
+    const bool x4 = ratio_x <= 1.5f && dst->cols % 4 == 0 && dst->stride % 4 == 0 && ((uintptr_t)dst->data & 15) == 0 && b.dst_frame % 16 == 0;
     const int tx = x4 ? (int)ceil_div(dst->cols, 256) : tiles_x;
     const uint64_t tiles = (uint64_t)tx * tiles_y;
     if (tiles > 0x7fffffffu || n > MAX_FRAMES_PER_LAUNCH) return -1;
     const dim3 grid((unsigned)tiles, n);
-    const FrameSpan fr{src_frame, dst_frame};
+    const FrameSpan fr = b.span();
 #define ZG_RB(NPX) \
     switch (form) { \
     case 1: hipLaunchKernelGGL((k_resize_bilinear_rgba8<NPX, 1, false, 1>), grid, dim3(64), 0, s, dimg(src), dimg(dst), ratio_x, ratio_y, tx, fr); break; \
@@ -430,39 +432,40 @@ int resize_bilinear_rgba8_frames(const zg_image *src, const zg_image *dst, uint3
 }
 
 template <int PIX, int CLS, int KIND, int T>
-static int launch_planes(const zg_image *src, const zg_image *dst, const AxisTable &tx, const AxisTable &ty, uint32_t n, const FrameSpan &fr, hipStream_t s) {
+static int launch_planes(const FrameBatch &b, const AxisTable &tx, const AxisTable &ty, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
     const int tiles_x = (int)ceil_div(dst->cols, 64), tiles_y = (int)ceil_div(dst->rows, 4);
     const float ratio_x = (float)src->cols / (float)dst->cols, ratio_y = (float)src->rows / (float)dst->rows;
     if constexpr (PIX == ZG_PIXEL_RGBA_U8 && CLS == RC_BILINEAR) {
-        const int rcb = resize_bilinear_rgba8_frames(src, dst, n, fr.src_frame, fr.dst_frame, s);
+        const int rcb = resize_bilinear_rgba8_frames(b, s);
         if (rcb >= 0) return rcb;
     }
-    if (n > MAX_FRAMES_PER_LAUNCH) return -1;
-    hipLaunchKernelGGL((k_resize_planes<PIX, CLS, KIND, T>), dim3((unsigned)(tiles_x * tiles_y), n), dim3(256), 0, s, dimg(src), dimg(dst), tx, ty,
-                       ratio_x, ratio_y, tiles_x, fr);
+    if (b.n > MAX_FRAMES_PER_LAUNCH) return -1;
+    hipLaunchKernelGGL((k_resize_planes<PIX, CLS, KIND, T>), dim3((unsigned)(tiles_x * tiles_y), b.n), dim3(256), 0, s, dimg(src), dimg(dst), tx, ty,
+                       ratio_x, ratio_y, tiles_x, b.span());
     return launch_ok();
 }
 
 template <int PIX>
-static int resize_planes_pix(const zg_image *src, const zg_image *dst, int kind, const AxisTable &tx, const AxisTable &ty, uint32_t n, const FrameSpan &fr, hipStream_t s) {
+static int resize_planes_pix(const FrameBatch &b, int kind, const AxisTable &tx, const AxisTable &ty, hipStream_t s) {
     switch (kind) {
-    case ZG_INTERP_NEAREST: return launch_planes<PIX, RC_NEAREST, ZG_INTERP_NEAREST, 1>(src, dst, tx, ty, n, fr, s);
-    case ZG_INTERP_BILINEAR: return launch_planes<PIX, RC_BILINEAR, ZG_INTERP_BILINEAR, 2>(src, dst, tx, ty, n, fr, s);
-    case ZG_INTERP_LANCZOS: return launch_planes<PIX, RC_LANCZOS, ZG_INTERP_LANCZOS, 6>(src, dst, tx, ty, n, fr, s);
-    case ZG_INTERP_BICUBIC: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_BICUBIC, 4>(src, dst, tx, ty, n, fr, s);
-    case ZG_INTERP_CATMULL_ROM: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_CATMULL_ROM, 4>(src, dst, tx, ty, n, fr, s);
-    default: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_MITCHELL, 4>(src, dst, tx, ty, n, fr, s);
+    case ZG_INTERP_NEAREST: return launch_planes<PIX, RC_NEAREST, ZG_INTERP_NEAREST, 1>(b, tx, ty, s);
+    case ZG_INTERP_BILINEAR: return launch_planes<PIX, RC_BILINEAR, ZG_INTERP_BILINEAR, 2>(b, tx, ty, s);
+    case ZG_INTERP_LANCZOS: return launch_planes<PIX, RC_LANCZOS, ZG_INTERP_LANCZOS, 6>(b, tx, ty, s);
+    case ZG_INTERP_BICUBIC: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_BICUBIC, 4>(b, tx, ty, s);
+    case ZG_INTERP_CATMULL_ROM: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_CATMULL_ROM, 4>(b, tx, ty, s);
+    default: return launch_planes<PIX, RC_CUBIC_INT, ZG_INTERP_MITCHELL, 4>(b, tx, ty, s);
     }
 }
 
 // Image(Rgb(u8) / Rgba(u8)).resize for differing sizes; caller (resize_impl) has validated the images.
 int resize_planes_impl(const zg_image *src, const zg_image *dst, const zg_method *method, hipStream_t s) {
-    return resize_planes_frames(src, dst, method, 1, 0, 0, s);
+    return resize_planes_frames(FrameBatch{src, dst}, method, s);
 }
 
 // n frames of the same two shapes in one launch (frame = blockIdx.y); -1 past the grid's limit.
-int resize_planes_frames(const zg_image *src, const zg_image *dst, const zg_method *method, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
-    const FrameSpan fr{src_frame, dst_frame};
+int resize_planes_frames(const FrameBatch &b, const zg_method *method, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
     const int kind = method->kind;
     const int taps = kind == ZG_INTERP_NEAREST ? 1 : (kind == ZG_INTERP_BILINEAR ? 2 : (kind == ZG_INTERP_LANCZOS ? 6 : 4));
     AxisTable tx{}, ty{};
@@ -472,8 +475,8 @@ int resize_planes_frames(const zg_image *src, const zg_image *dst, const zg_meth
         if ((rc = axis_table(kind, src->cols, dst->cols, taps, tx, hold_x, s))) return rc;
         if ((rc = axis_table(kind, src->rows, dst->rows, taps, ty, hold_y, s))) return rc;
     }
-    if (src->pixel == ZG_PIXEL_RGB_U8) return resize_planes_pix<ZG_PIXEL_RGB_U8>(src, dst, kind, tx, ty, n, fr, s);
-    return resize_planes_pix<ZG_PIXEL_RGBA_U8>(src, dst, kind, tx, ty, n, fr, s);
+    if (src->pixel == ZG_PIXEL_RGB_U8) return resize_planes_pix<ZG_PIXEL_RGB_U8>(b, kind, tx, ty, s);
+    return resize_planes_pix<ZG_PIXEL_RGBA_U8>(b, kind, tx, ty, s);
 }
 
 
@@ -504,8 +507,8 @@ int resize_lanczos_weights_impl(const zg_image *src, const zg_image *dst, const 
     int32_t *dev = (int32_t *)block.p;
     if ((rc = upload_pageable(dev, host.data(), host.size() * 4, s))) return rc;
     const AxisTable tx{dev, dev + nx}, ty{dev + 2 * nx, dev + 2 * nx + ny};
-    return src->pixel == ZG_PIXEL_RGB_U8 ? resize_planes_pix<ZG_PIXEL_RGB_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s)
-                                         : resize_planes_pix<ZG_PIXEL_RGBA_U8>(src, dst, ZG_INTERP_LANCZOS, tx, ty, 1, FrameSpan{0, 0}, s);
+    return src->pixel == ZG_PIXEL_RGB_U8 ? resize_planes_pix<ZG_PIXEL_RGB_U8>(FrameBatch{src, dst}, ZG_INTERP_LANCZOS, tx, ty, s)
+                                         : resize_planes_pix<ZG_PIXEL_RGBA_U8>(FrameBatch{src, dst}, ZG_INTERP_LANCZOS, tx, ty, s);
 }
 
 } // namespace zg

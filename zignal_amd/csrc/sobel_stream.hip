@@ -195,14 +195,16 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
 }
 
 template <int SP>
-static int launch_sobel_stream(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
+static int launch_sobel_stream(const FrameBatch &b, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
+    const uint32_t n = b.n;
     SobelStreamArgs a;
     a.src = (const uint8_t *)src->data;
     a.dst = (uint8_t *)dst->data;
     a.src_pitch = src->stride * (size_t)SP;
     a.dst_pitch = dst->stride;
-    a.src_frame = src_frame;
-    a.dst_frame = dst_frame;
+    a.src_frame = b.src_frame;
+    a.dst_frame = b.dst_frame;
     a.rows = (int32_t)src->rows;
     a.row_bytes = (int32_t)(src->cols * (uint32_t)SP);
     a.strips_x = (int32_t)ceil_div((unsigned)a.row_bytes, 1024u);
@@ -221,16 +223,17 @@ static int launch_sobel_stream(const zg_image *src, const zg_image *dst, uint32_
 }
 
 // Returns -1 when the preconditions do not hold (the caller runs k_sobel).
-int try_sobel_stream(const zg_image *src, const zg_image *dst, uint32_t n, size_t src_frame, size_t dst_frame, hipStream_t s) {
+int try_sobel_stream(const FrameBatch &b, hipStream_t s) {
+    const zg_image *src = b.src, *dst = b.dst;
     if (src->pixel != ZG_PIXEL_U8 && src->pixel != ZG_PIXEL_RGBA_U8) return -1;
     const int sp = src->pixel == ZG_PIXEL_U8 ? 1 : 4;
     const uint64_t rb = (uint64_t)src->cols * (uint64_t)sp, sp_pitch = (uint64_t)src->stride * sp;
     const unsigned dalign = sp == 1 ? 16 : 4; // the lane's output unit
-    if (rb % 16 || sp_pitch % 16 || src_frame % 16 || ((uintptr_t)src->data & 15)) return -1;
-    if (dst->stride % dalign || dst_frame % dalign || ((uintptr_t)dst->data & (dalign - 1))) return -1;
+    if (rb % 16 || sp_pitch % 16 || b.src_frame % 16 || ((uintptr_t)src->data & 15)) return -1;
+    if (dst->stride % dalign || b.dst_frame % dalign || ((uintptr_t)dst->data & (dalign - 1))) return -1;
     if (rb % 1024 == 16) return -1; // the last strip would be one lane wide
     if (src->cols < 64 || src->rows < 16 || rb > 0x3fffffffu || sp_pitch > 0x7fffffffu || dst->stride > 0x7fffffffu) return -1;
-    return sp == 1 ? launch_sobel_stream<1>(src, dst, n, src_frame, dst_frame, s) : launch_sobel_stream<4>(src, dst, n, src_frame, dst_frame, s);
+    return sp == 1 ? launch_sobel_stream<1>(b, s) : launch_sobel_stream<4>(b, s);
 }
 
 } // namespace zg
