@@ -330,23 +330,32 @@ def test_a_block_goes_round_three_streams_twice(oracle):
     rotation(_rotation_op(oracle))
 
 
-def _child(body, env=None, timeout=600):
-    code = ("import sys; sys.path.insert(0, %r)\nfrom oracle import pyoracle as o; o.lib()\nimport tests.test_gpu_concurrency as T\n%s\nprint('ok')\n" % (ROOT, body))
+def _child(body, env=None, timeout=600, module="tests.test_gpu_concurrency"):
+    """`body` in a fresh process, with the oracle as `o` and `module` (this one, or one that extends it) as `T`."""
+    code = ("import sys; sys.path.insert(0, %r)\nfrom oracle import pyoracle as o; o.lib()\nimport %s as T\n%s\nprint('ok')\n" % (ROOT, module, body))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=dict(os.environ, **(env or {})))
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-3000:] + out.stderr[-3000:]
     return out.stdout
+
+
+def _share_wants():
+    """One directory for every child process of a session: what this process has computed is written there, and whichever input has no
+    file yet is computed in the child that first needs it and kept."""
+    if WANTS_DIR not in os.environ:
+        import tempfile
+        _WANTS["dir"] = tempfile.TemporaryDirectory()
+        os.environ[WANTS_DIR] = _WANTS["dir"].name
+    for (name, seed), (_, want) in [kv for kv in _WANTS.items() if kv[0] != "dir"]:
+        path = os.path.join(os.environ[WANTS_DIR], f"{name}-{seed}.npz")
+        if not os.path.exists(path):
+            np.savez(path, *want)
 
 
 @pytest.mark.parametrize("cap_mb", ("16", "0"))
 def test_a_capped_cache_frees_blocks_with_events_pending_and_changes_nothing(cap_mb):
     """ZIGNAL_HIP_SCRATCH_CACHE_MB is read once: a child process. Past the cap a freed block goes back to the driver while the call that used
     it is still queued, so nothing is handed over and the window conditions do not apply; every result must still equal the oracle."""
-    if WANTS_DIR not in os.environ:  # one directory for both children; whichever input has no file yet is computed there and kept
-        import tempfile
-        _WANTS["dir"] = tempfile.TemporaryDirectory()
-        os.environ[WANTS_DIR] = _WANTS["dir"].name
-        for (name, seed), (_, want) in [kv for kv in _WANTS.items() if kv[0] != "dir"]:
-            np.savez(os.path.join(os.environ[WANTS_DIR], f"{name}-{seed}.npz"), *want)
+    _share_wants()
     print(_child("T.section_a_all(o, check_window=False)", {"ZIGNAL_HIP_SCRATCH_CACHE_MB": cap_mb}))
 
 
