@@ -12,8 +12,10 @@
 
 static inline ZT ZN(clampv)(ZT v, ZT lo, ZT hi) { return v < lo ? lo : (v > hi ? hi : v); } /* std.math.clamp for every ordered v; a NaN passes through here where @max(lo, @min(v, hi)) gives hi: the kernels (colorspaces.hip: cs_clamp) do the same, the byte step after it (color.c: unit_to_u8) follows the reference, and an f32 destination that a NaN reaches differs from the reference */
 static inline ZT ZN(lerp)(ZT a, ZT b, ZT t) { return ZFMA(b - a, t, a); }                     /* std.math.lerp = @mulAdd(b - a, t, a) */
-static inline ZT ZN(maxv)(ZT a, ZT b) { return a > b ? a : b; }
-static inline ZT ZN(minv)(ZT a, ZT b) { return a < b ? a : b; }
+/* @max / @min: the other operand when one is a NaN. Of +0.0 and -0.0 the reference's compiler may return either (llvm.maxnum / minnum);
+ * here -0.0 orders below +0.0, as IEEE 754-2019 maximum / minimum and the kernels' fmaxf / fminf (v_max_f32 / v_min_f32) have it. */
+static inline ZT ZN(maxv)(ZT a, ZT b) { return a != a ? b : (b != b ? a : (a == b ? (signbit(a) ? b : a) : (a > b ? a : b))); }
+static inline ZT ZN(minv)(ZT a, ZT b) { return a != a ? b : (b != b ? a : (a == b ? (signbit(a) ? a : b) : (a < b ? a : b))); }
 /* Zig's float @mod: r = fmod(x, y); x < 0 ? fmod(r + y, y) : r (LLVM lowering of airMod) */
 static inline ZT ZN(zmod)(ZT x, ZT y) {
     const ZT a = ZFMOD(x, y);
@@ -182,7 +184,8 @@ static void ZN(hsl_to_rgb)(const ZT hsl[3], ZT out[3]) { /* color.zig:1111-1147 
     const ZT h = ZN(zmod)(hsl[0], 360);
     const ZT s = ZN(clampv)(hsl[1] / 100, 0, 1), l = ZN(clampv)(hsl[2] / 100, 0, 1);
     const ZT hue_sector = h / ZC(60.0);
-    const uint64_t sector = (uint64_t)ZTRUNC(hue_sector);
+    /* the conversion of a NaN to usize (:1118; a hue of +-inf or NaN: @mod gives NaN) is illegal behaviour in the reference and undefined in C: sector 0 here and in the kernel */
+    const uint64_t sector = hue_sector == hue_sector ? (uint64_t)ZTRUNC(hue_sector) : 0;
     const ZT f = hue_sector - (ZT)sector;
     const ZT factors[6][3] = {{1, f, 0}, {1 - f, 1, 0}, {0, 1, f}, {0, 1 - f, 1}, {f, 0, 1}, {1, 0, 1 - f}};
     const unsigned idx = (unsigned)(sector % 6);

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import zignal_amd as zg
-from tests.util import assert_bits_equal, synth
+from tests.util import assert_bits_equal, assert_bits_equal_nan_class, synth
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -29,8 +29,8 @@ def channels(space):
 
 
 def every_colour_frame():
-    """All 2^24 Rgb(u8) colours would be 48 MB; a 3-D lattice of 64^3 plus the corners of the cube is enough to hit every
-    branch (hue sectors, both sRGB and Lab transfer segments, greys)."""
+    """The fast suite's sample of the Rgb(u8) cube: a 3-D lattice of 64^3 with the corners of the cube, which hits every branch (hue
+    sectors, both sRGB and Lab transfer segments, greys). The proof is tests/test_gpu_color_exhaustive.py: all 2^24 colours."""
     g = np.linspace(0, 255, 64).round().astype(np.uint8)
     r, gg, b = np.meshgrid(g, g, g, indexing="ij")
     cube = np.stack([r, gg, b], -1).reshape(512, 512, 3)
@@ -154,3 +154,31 @@ def test_lab_to_u8_four_pixels_per_lane(oracle):
                 if name == "wild":  # a NaN component clamps to 1 (std.math.clamp = @max(0, @min(v, 1)), color.zig:53,377-379): the bytes are 255
                     assert want[-1, -1].tolist() == [255] * ch, (rows, cols, ch)
                 assert_bits_equal(run(src, zg.CS_LAB, space, np.uint8), want, f"{rows}x{cols} {name} -> {ch} channels")
+
+
+def test_values_the_reference_leaves_open(oracle):
+    """The three differences tests/test_gpu_color_pairs.py found between kernel and oracle, as named cases (DESIGN.md 4): none is a colour;
+    each is a value where the reference's own result is another operand, either operand, or no result at all."""
+    nan, inf, f32 = np.float32(np.nan), np.float32(np.inf), np.float32
+
+    def same(src, a, b, dtype):
+        with np.errstate(all="ignore"):
+            want = oracle.convert(src, a, b, dtype, channels(b))
+        assert_bits_equal_nan_class(run(src, a, b, dtype), want, f"space {a} -> {b} {np.dtype(dtype).name}")
+        return want
+
+    # a NaN grey -> Lab: xyzToLab's @max(0, 116 fy - 16) (color.zig:1302) returns its other operand for a NaN, so L is 0 beside NaN a and b
+    want = same(np.full((3, 5), nan, f32), zg.CS_GRAY, zg.CS_LAB, f32)
+    assert want[0, 0].view(np.uint32)[0] == 0 and np.isnan(want[0, 0, 1:]).all()
+    # Ycbcr(-0, -0, -0) is Rgb(-0, +0, -0): rgbToHsv / rgbToHsl take @max of both zeros (color.zig:1090, 1153); -0 orders below +0
+    zeros = np.full((3, 5, 3), -0.0, f32)
+    assert same(zeros, zg.CS_YCBCR, zg.CS_RGB, f32)[0, 0].view(np.uint32).tolist() == [0x80000000, 0, 0x80000000]
+    for dst in (zg.CS_HSV, zg.CS_HSL):
+        assert same(zeros, zg.CS_YCBCR, dst, f32)[0, 0].view(np.uint32).tolist() == [0, 0, 0]
+    # Hsl with an infinite hue: @mod gives NaN, whose conversion to usize (color.zig:1118) has no result in the reference; sector 0 on both sides
+    hsl = np.array([[(inf, 50, 50), (-inf, 50, 50), (inf, inf, inf), (-inf, -inf, -inf), (nan, 50, 50)]], f32).repeat(2, 0)
+    want = same(hsl, zg.CS_HSL, zg.CS_RGB, f32)
+    assert np.isnan(want[0, 2]).tolist() == [False, True, False] and want[0, 2, 0] == 1 and want[0, 2, 2] == 1
+    same(hsl, zg.CS_HSL, zg.CS_RGB, np.uint8)
+    same(hsl, zg.CS_HSL, zg.CS_RGBA, np.uint8)
+    same(hsl, zg.CS_HSL, zg.CS_LAB, f32)

@@ -198,7 +198,8 @@ __device__ inline void apply_hop(int cur, int nxt, float (&v)[4], const float *l
             const float h = cs_mod(v[0], 360.0f);
             const float s = cs_clamp(v[1] / 100, 0.0f, 1.0f), l = cs_clamp(v[2] / 100, 0.0f, 1.0f);
             const float hue_sector = h / 60.0f;
-            const unsigned long long sector = (unsigned long long)truncf(hue_sector);
+            // a hue of +-inf or NaN leaves cs_mod as NaN, whose conversion to usize (:1118) is illegal behaviour in the reference: sector 0, as the oracle
+            const unsigned long long sector = hue_sector == hue_sector ? (unsigned long long)truncf(hue_sector) : 0ull;
             const float f = hue_sector - (float)sector;
             float fr, fg, fb;
             switch ((int)(sector % 6)) {

@@ -812,17 +812,10 @@ int zg_graph_end_capture(zg_stream stream, zg_graph *out) {
         capture_id = remembered;
         known = true;
     }
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(s, &g);
-    const char *what = "hipStreamEndCapture";
-    hipGraphExec_t exec = nullptr;
-    if (e == hipSuccess) {
-        e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-        what = "hipGraphInstantiate";
-    }
-    if (g) (void)hipGraphDestroy(g);
-    // the scratch and the tables this capture took now belong to the graph, or go back at once if there is no graph to own them
-    // (a failed end or instantiation included)
+    // The scratch and the tables this capture took are claimed BEFORE the capture ends. Once hipStreamEndCapture returns the stream no
+    // longer reports a capture, and until the graph owns them (an instantiation later) another thread's zg_release_graph_scratch would take
+    // these blocks for those of a capture ended elsewhere and free them: the graph's kernels then wrote into memory that the next
+    // hipMalloc hands to somebody else's eager call.
     GraphOwned mine;
     if (known) {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
@@ -842,7 +835,20 @@ int zg_graph_end_capture(zg_stream stream, zg_graph *out) {
                 ++i;
             }
         }
-        if (e == hipSuccess && (!mine.blocks.empty() || !mine.holds.empty())) g_graph_owned[(void *)exec] = std::move(mine);
+    }
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    const char *what = "hipStreamEndCapture";
+    hipGraphExec_t exec = nullptr;
+    if (e == hipSuccess) {
+        e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+        what = "hipGraphInstantiate";
+    }
+    if (g) (void)hipGraphDestroy(g);
+    // they now belong to the graph, or go back at once if there is no graph to own them (a failed end or instantiation included)
+    if (e == hipSuccess && (!mine.blocks.empty() || !mine.holds.empty())) {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        g_graph_owned[(void *)exec] = std::move(mine);
     }
     if (e != hipSuccess) {
         release_graph_memory(mine.blocks, mine.holds);
