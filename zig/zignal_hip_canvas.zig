@@ -1,4 +1,4 @@
-//! zignal_hip_canvas.zig — the Canvas module of the shim: Canvas(T)'s lines, rectangles, circles, polygons, Bézier curves and spline polygons (reference
+//! zignal_hip_canvas.zig — the Canvas module of the shim: Canvas(T)'s lines, rectangles, circles, arcs, polygons, Bézier curves and spline polygons (reference
 //! src/canvas/Canvas.zig) through libzignal_hip.so's zg_canvas_* entry points (include/zignal_hip_canvas.h). Like the other files of
 //! the shim it has not been compiled where the library is built (no Zig toolchain).
 const std = @import("std");
@@ -10,6 +10,7 @@ pub const c = struct {
     pub extern fn zg_sizeof_draw_cmd() usize;
     pub extern fn zg_canvas_tile() u32;
     pub extern fn zg_canvas_draw(img: *const hip.c.ZgImage, cmds: ?[*]const ZgDrawCmd, n: u32, count_device: ?*const u32, vertices: ?[*]const f32, n_vertices: u32, stream: ?*anyopaque) c_int;
+    pub extern fn zg_canvas_draw_arcs(img: *const hip.c.ZgImage, cmds: ?[*]const ZgDrawCmd, n: u32, count_device: ?*const u32, vertices: ?[*]const f32, n_vertices: u32, stream: ?*anyopaque) c_int;
     pub extern fn zg_canvas_draw_host(img: *const hip.c.ZgImage, cmds: ?[*]const ZgDrawCmd, n: u32, vertices: ?[*]const f32, n_vertices: u32) c_int;
     pub extern fn zg_canvas_cmds_from_hough_lines(lines: ?*const anyopaque, counts: *const u32, capacity: u32, color: *const [4]u8, width: u32, mode: c_int, cmds_out: ?[*]ZgDrawCmd, count_out: *u32, stream: ?*anyopaque) c_int;
     pub extern fn zg_canvas_cmds_from_keypoints(keypoints: ?*const anyopaque, count: *const u32, capacity: u32, radius: f32, color: *const [4]u8, width: u32, mode: c_int, cmds_out: ?[*]ZgDrawCmd, count_out: *u32, stream: ?*anyopaque) c_int;
@@ -19,7 +20,7 @@ comptime {
     std.debug.assert(@sizeOf(c.ZgDrawCmd) == 40);
 }
 
-pub const Kind = enum(i32) { line = 0, rectangle = 1, fill_rectangle = 2, circle = 3, fill_circle = 4, polygon = 5, fill_polygon = 6, quad_bezier = 18, cubic_bezier = 19, spline_polygon = 20, fill_spline_polygon = 21 };
+pub const Kind = enum(i32) { line = 0, rectangle = 1, fill_rectangle = 2, circle = 3, fill_circle = 4, polygon = 5, fill_polygon = 6, arc = 16, fill_arc = 17, quad_bezier = 18, cubic_bezier = 19, spline_polygon = 20, fill_spline_polygon = 21 };
 /// ZG_CANVAS_MAX_CURVE_POINTS: the points a filled spline polygon may tessellate into
 pub const max_curve_points: u32 = 512;
 pub const DrawMode = zignal.DrawMode;
@@ -37,7 +38,7 @@ fn pixelOf(comptime T: type) c_int {
 }
 
 /// Canvas(T) over a host Image(T): the draw methods append to a command list, flush() executes it in list order through
-/// zg_canvas_draw_host and empties it. The result equals the reference's Canvas(T) making the same calls, byte for byte.
+/// zg_canvas_draw_host (which sees the list and takes the kernel that knows arcs only when it holds one) and empties it. The result equals the reference's Canvas(T) making the same calls, byte for byte.
 pub fn Canvas(comptime T: type) type {
     return struct {
         image: zignal.Image(T),
@@ -85,6 +86,20 @@ pub fn Canvas(comptime T: type) type {
         pub fn fillCircle(self: *Self, center: Point, radius: f32, color: Rgba, mode: DrawMode) !void {
             try self.add(.fill_circle, mode, 1, color, .{ center.x(), center.y(), radius, 0 });
         }
+        /// The two angles travel as one entry of the vertex array; any finite angle, normalised as the reference's ArcRange does.
+        pub fn drawArc(self: *Self, center: Point, radius: f32, start_angle: f32, end_angle: f32, color: Rgba, width: u32, mode: DrawMode) !void {
+            try self.addArc(.arc, center, radius, start_angle, end_angle, mode, width, color);
+        }
+        pub fn fillArc(self: *Self, center: Point, radius: f32, start_angle: f32, end_angle: f32, color: Rgba, mode: DrawMode) !void {
+            try self.addArc(.fill_arc, center, radius, start_angle, end_angle, mode, 1, color);
+        }
+        fn addArc(self: *Self, kind: Kind, center: Point, radius: f32, start_angle: f32, end_angle: f32, mode: DrawMode, width: u32, color: Rgba) !void {
+            const first: u32 = @intCast(self.vertices.items.len / 2);
+            try self.vertices.appendSlice(self.allocator, &.{ start_angle, end_angle });
+            try self.add(kind, mode, width, color, .{ center.x(), center.y(), radius, 0 });
+            self.cmds.items[self.cmds.items.len - 1].first_vertex = first;
+            self.cmds.items[self.cmds.items.len - 1].n_vertices = 1;
+        }
         pub fn drawPolygon(self: *Self, polygon: []const Point, color: Rgba, width: u32, mode: DrawMode) !void {
             try self.addPolygon(.polygon, polygon, mode, width, color);
         }
@@ -120,6 +135,13 @@ pub fn Canvas(comptime T: type) type {
 pub fn drawInto(image: hip.c.ZgImage, cmds: [*]const c.ZgDrawCmd, n: u32, count_device: ?*const u32, vertices: ?[*]const f32, n_vertices: u32, stream: ?*anyopaque) !void {
     if (c.zg_sizeof_draw_cmd() != @sizeOf(c.ZgDrawCmd)) return error.AbiMismatch;
     try hip.check(c.zg_canvas_draw(&image, cmds, n, count_device, vertices, n_vertices, stream));
+}
+
+/// drawInto for a list that may hold .arc or .fill_arc commands (zg_canvas_draw_arcs; drawInto skips them): the caller who built the
+/// device list knows whether it may.
+pub fn drawArcsInto(image: hip.c.ZgImage, cmds: [*]const c.ZgDrawCmd, n: u32, count_device: ?*const u32, vertices: ?[*]const f32, n_vertices: u32, stream: ?*anyopaque) !void {
+    if (c.zg_sizeof_draw_cmd() != @sizeOf(c.ZgDrawCmd)) return error.AbiMismatch;
+    try hip.check(c.zg_canvas_draw_arcs(&image, cmds, n, count_device, vertices, n_vertices, stream));
 }
 
 /// One line command per line of zg_hough_find_lines' device list; counts is that call's two device words.

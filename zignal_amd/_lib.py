@@ -142,7 +142,8 @@ class ZgDrawCmd(C.Structure):
 
 
 DRAW_LINE, DRAW_RECT, DRAW_FILL_RECT, DRAW_CIRCLE, DRAW_FILL_CIRCLE, DRAW_POLYGON, DRAW_FILL_POLYGON = range(7)
-DRAW_QUAD_BEZIER, DRAW_CUBIC_BEZIER, DRAW_SPLINE_POLYGON, DRAW_FILL_SPLINE_POLYGON = range(18, 22)  # 7-17 are no kinds
+DRAW_ARC, DRAW_FILL_ARC = 16, 17  # zg_canvas_draw_arcs and the host form only; 7-15 are no kinds
+DRAW_QUAD_BEZIER, DRAW_CUBIC_BEZIER, DRAW_SPLINE_POLYGON, DRAW_FILL_SPLINE_POLYGON = range(18, 22)
 DRAW_FAST, DRAW_SOFT = range(2)
 CANVAS_MAX_VERTICES, CANVAS_MAX_COORD, CANVAS_MAX_WIDTH, CANVAS_MAX_SIZE, CANVAS_MAX_COMMANDS = 64, 65536.0, 65536, 32768, 1 << 24  # ZG_CANVAS_MAX_*
 CANVAS_MAX_CURVE_POINTS = 512
@@ -450,6 +451,7 @@ _CANVAS_SIGNATURES = {
     "zg_sizeof_draw_cmd": [],
     "zg_canvas_tile": [],
     "zg_canvas_draw": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "zg_canvas_draw_arcs": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
     "zg_canvas_draw_host": [_IMG, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32],
     "zg_canvas_cmds_from_hough_lines": [C.c_void_p, C.c_void_p, C.c_uint32, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "zg_canvas_cmds_from_keypoints": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],

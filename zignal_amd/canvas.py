@@ -79,10 +79,19 @@ def _bytes_of(t) -> int:
     return t.numel() * t.element_size()
 
 
-def draw(image, cmds, count=None, vertices=None, n=None) -> None:
+def has_arcs(commands) -> bool:
+    """Does a list of command dicts, or a DRAW_CMD_DTYPE array, hold a drawArc or fillArc? Such a list goes to zg_canvas_draw_arcs."""
+    if isinstance(commands, np.ndarray):
+        return bool(np.isin(commands["kind"], (L.DRAW_ARC, L.DRAW_FILL_ARC)).any())
+    return any(int(c["kind"]) in (L.DRAW_ARC, L.DRAW_FILL_ARC) for c in commands)
+
+
+def draw(image, cmds, count=None, vertices=None, n=None, arcs=False) -> None:
     """zg_canvas_draw, the device-list form: `cmds` is a device tensor holding zg_draw_cmd structs (n of them; by default as many as it
     holds), `count` an optional device tensor whose first 4 bytes are the number of commands to execute (at most n), `vertices` a
-    float32 device tensor of (x, y) pairs. Asynchronous on the current stream; nothing is synchronised, copied or uploaded."""
+    float32 device tensor of (x, y) pairs. Asynchronous on the current stream; nothing is synchronised, copied or uploaded.
+    arcs=True: zg_canvas_draw_arcs, the entry point that also draws DRAW_ARC and DRAW_FILL_ARC (zg_canvas_draw skips them); the host
+    cannot see a device list, so the caller who built it says whether it may hold arcs."""
     img = image if isinstance(image, Image) else Image(image)
     if not img.on_device or not _is_torch(cmds) or (count is not None and not _is_torch(count)) or (vertices is not None and not _is_torch(vertices)):
         raise ValueError("draw takes a device image and device tensors")
@@ -94,9 +103,10 @@ def draw(image, cmds, count=None, vertices=None, n=None) -> None:
         raise ValueError("vertices must be a contiguous float32 tensor of (x, y) pairs")
     nv = 0 if vertices is None else vertices.numel() // 2
     d = img._desc()
+    entry = L.lib().zg_canvas_draw_arcs if arcs else L.lib().zg_canvas_draw
     with torch.cuda.device(img.data.device):
-        L.check(L.lib().zg_canvas_draw(C.byref(d), C.c_void_p(cmds.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
-                                       C.c_void_p(vertices.data_ptr()) if nv else None, nv, img._stream()))
+        L.check(entry(C.byref(d), C.c_void_p(cmds.data_ptr()), n, C.c_void_p(count.data_ptr()) if count is not None else None,
+                      C.c_void_p(vertices.data_ptr()) if nv else None, nv, img._stream()))
 
 
 def _builder_out(list_tensor, itemsize, cmds_out, count_out):
@@ -186,9 +196,19 @@ class Canvas:
         """At most CANVAS_MAX_CURVE_POINTS points once tessellated (3 pixels a segment, 4 to 50 points an edge)."""
         return self._add(L.DRAW_FILL_SPLINE_POLYGON, color, 1, mode, p=(tension,), pts=points)
 
+    def draw_arc(self, center, radius: float, start_angle: float, end_angle: float, color, width: int = 1, mode="fast"):
+        """Angles in radians from the positive x axis towards positive y, any finite value (normalised as the reference does); a span of
+        2 pi or more is the circle, a NaN or infinite angle draws nothing."""
+        return self._add(L.DRAW_ARC, color, width, mode, (center[0], center[1], radius), pts=((start_angle, end_angle),))
+
+    def fill_arc(self, center, radius: float, start_angle: float, end_angle: float, color, mode="fast"):
+        """The pie slice between the two angles (see draw_arc)."""
+        return self._add(L.DRAW_FILL_ARC, color, 1, mode, (center[0], center[1], radius), pts=((start_angle, end_angle),))
+
     def flush(self, stream=None) -> None:
-        """Draw the list and empty it. Device image: the two lists are uploaded (one synchronous copy each) and zg_canvas_draw runs on
-        `stream` (a torch stream; default: the current one). Host image: zg_canvas_draw_host."""
+        """Draw the list and empty it. Device image: the two lists are uploaded (one synchronous copy each) and zg_canvas_draw — or
+        zg_canvas_draw_arcs when the list holds an arc — runs on `stream` (a torch stream; default: the current one). Host image:
+        zg_canvas_draw_host."""
         commands, self.commands = self.commands, []
         if not commands:
             return
@@ -199,15 +219,16 @@ class Canvas:
         dev = self.image.data.device
         dcmds = torch.from_numpy(cmds.view(np.uint8)).to(dev)
         dverts = torch.from_numpy(vertices).to(dev) if len(vertices) else None
+        arcs = has_arcs(cmds)
         if stream is None:
-            draw(self.image, dcmds, vertices=dverts)
+            draw(self.image, dcmds, vertices=dverts, arcs=arcs)
         else:
             with torch.cuda.stream(stream):
-                draw(self.image, dcmds, vertices=dverts)
+                draw(self.image, dcmds, vertices=dverts, arcs=arcs)
             dcmds.record_stream(stream)
             if dverts is not None:
                 dverts.record_stream(stream)
 
-    def draw(self, cmds_tensor, count=None, vertices=None) -> None:
+    def draw(self, cmds_tensor, count=None, vertices=None, arcs=False) -> None:
         """The device-list form: see zignal_amd.canvas.draw."""
-        draw(self.image, cmds_tensor, count, vertices)
+        draw(self.image, cmds_tensor, count, vertices, arcs=arcs)

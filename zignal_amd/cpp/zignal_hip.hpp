@@ -967,10 +967,10 @@ inline void HoughTransform::computeInto(const DeviceImage<uint8_t> &edges, const
 // ---- canvas: Canvas(T) (src/canvas/Canvas.zig) ----
 enum class DrawMode { fast = ZG_DRAW_FAST, soft = ZG_DRAW_SOFT };                         // Canvas.zig:19-24
 struct Point2 { float x, y; };
-// Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods (lines, rectangles, circles,
+// Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods (lines, rectangles, circles, arcs,
 // polygons, Bézier curves, spline polygons) append to a command list, flush()
 // executes it into the image in list order (zg_canvas_draw_host for host pixels; for device pixels the two lists are uploaded and
-// zg_canvas_draw runs on the image's stream) and empties it. The result equals the reference making the same calls, byte for byte.
+// zg_canvas_draw — zg_canvas_draw_arcs when the list holds an arc — runs on the image's stream) and empties it. The result equals the reference making the same calls, byte for byte.
 template <typename T, template <class> class Img = Image> class Canvas {
   public:
     static_assert(PixelTraits<T>::pixel == ZG_PIXEL_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGB_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGBA_U8,
@@ -992,6 +992,13 @@ template <typename T, template <class> class Img = Image> class Canvas {
     }
     Canvas &fillCircle(Point2 center, float radius, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) {
         return add(ZG_DRAW_FILL_CIRCLE, mode, 1, color, center.x, center.y, radius, 0.0f);
+    }
+    // angles in radians from the positive x axis towards positive y, any finite value; |end - start| >= 2 pi is the circle
+    Canvas &drawArc(Point2 center, float radius, float start_angle, float end_angle, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
+        return addArc(ZG_DRAW_ARC, center, radius, start_angle, end_angle, mode, width, color);
+    }
+    Canvas &fillArc(Point2 center, float radius, float start_angle, float end_angle, Rgba<uint8_t> color, DrawMode mode = DrawMode::fast) {
+        return addArc(ZG_DRAW_FILL_ARC, center, radius, start_angle, end_angle, mode, 1, color);
     }
     Canvas &drawPolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, uint32_t width = 1, DrawMode mode = DrawMode::fast) {
         return addPolygon(ZG_DRAW_POLYGON, polygon, mode, width, color);
@@ -1030,15 +1037,19 @@ template <typename T, template <class> class Img = Image> class Canvas {
             check(zg_malloc(&mem, cmd_bytes + vertices.size() * sizeof(float) + 256));
             int rc = zg_memcpy_h2d(mem, cmds.data(), cmds.size() * sizeof(zg_draw_cmd), image_->stream());
             if (!rc && nv) rc = zg_memcpy_h2d((char *)mem + cmd_bytes, vertices.data(), vertices.size() * sizeof(float), image_->stream());
-            if (!rc) rc = zg_canvas_draw(&d, (const zg_draw_cmd *)mem, n, nullptr, nv ? (const float *)((char *)mem + cmd_bytes) : nullptr, nv, image_->stream());
+            bool arcs = false; // the entry point whose kernel knows arcs only for a list that holds one
+            for (const zg_draw_cmd &c : cmds) arcs = arcs || c.kind == ZG_DRAW_ARC || c.kind == ZG_DRAW_FILL_ARC;
+            if (!rc) rc = (arcs ? zg_canvas_draw_arcs : zg_canvas_draw)(&d, (const zg_draw_cmd *)mem, n, nullptr, nv ? (const float *)((char *)mem + cmd_bytes) : nullptr, nv, image_->stream());
             (void)zg_free(mem); // waits for the draw that reads the lists
             check(rc);
         }
     }
     // the device-list form: every pointer is device memory; asynchronous, nothing is synchronised, recordable into a graph
-    void draw(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device = nullptr, const float *vertices = nullptr, uint32_t n_vertices = 0) const {
+    // arcs: zg_canvas_draw_arcs, for a list that may hold ZG_DRAW_ARC or ZG_DRAW_FILL_ARC (zg_canvas_draw skips them)
+    void draw(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device = nullptr, const float *vertices = nullptr, uint32_t n_vertices = 0,
+              bool arcs = false) const {
         const zg_image d = image_->desc();
-        check(zg_canvas_draw(&d, cmds, n, count_device, vertices, n_vertices, image_->stream()));
+        check((arcs ? zg_canvas_draw_arcs : zg_canvas_draw)(&d, cmds, n, count_device, vertices, n_vertices, image_->stream()));
     }
 
   private:
@@ -1055,6 +1066,13 @@ template <typename T, template <class> class Img = Image> class Canvas {
         cmds_.back().first_vertex = (uint32_t)(vertices_.size() / 2);
         cmds_.back().n_vertices = (uint32_t)polygon.size();
         for (const Point2 &p : polygon) { vertices_.push_back(p.x); vertices_.push_back(p.y); }
+        return *this;
+    }
+    Canvas &addArc(int kind, Point2 center, float radius, float start_angle, float end_angle, DrawMode mode, uint32_t width, Rgba<uint8_t> color) {
+        add(kind, mode, width, color, center.x, center.y, radius, 0.0f);
+        cmds_.back().first_vertex = (uint32_t)(vertices_.size() / 2); // the angle pair is one entry of the vertex array
+        cmds_.back().n_vertices = 1;
+        vertices_.push_back(start_angle); vertices_.push_back(end_angle);
         return *this;
     }
     const Img<T> *image_;

@@ -5,6 +5,8 @@
 //   drawCircle, fillCircle :636-644, :752-876, :1021-1084 (drawBresenhamCircle, renderRing, fillCircleFast's spans)
 //   drawQuadraticBezier, drawCubicBezier :1221-1275, :1360-1455 (tessellated by the lanes into LDS, then drawLine per segment in order)
 //   drawSplinePolygon, fillSplinePolygon :1280-1355, :1460-1472 (a cubic per edge; the fill is one fillPolygon over all edges' points)
+//   drawArc, fillArc :646-750, :878-927, :1039-1218 (ArcRange; the gated Bresenham circle and ring, the soft outline as lines or one polygon,
+//                             fillArcFast's spans, fillArcSoft's coverage) — in k_canvas<PIX, true> only, behind zg_canvas_draw_arcs
 // composited with Rgba.blend(.normal) and convertColor exactly as Image.insert does (zg_blend.h).
 //
 // The reference's result at a pixel is a fold, in call order, over every write any call makes to that pixel, and blending writes do not
@@ -12,7 +14,8 @@
 // command list in order, applies each write that reaches its pixel — as often as the reference makes it — and stores once if anything did.
 //   k_canvas_prep   one lane per command: checks the command against the contract and writes the pixel box that bounds everything the command
 //                   can write (empty for a command that is skipped, draws nothing or lies past the count word)
-//   k_canvas        per tile: 1024 commands at a time, each lane tests four commands' boxes against the tile and the hits are compacted in list
+//   k_canvas        (<PIX, false>: every kind but the arcs, zg_canvas_draw; <PIX, true>: the arcs too, zg_canvas_draw_arcs — the routines are shared,
+//                   what knows an arc is compiled into the second only, so the first is the kernel it was before there were arcs) per tile: 1024 commands at a time, each lane tests four commands' boxes against the tile and the hits are compacted in list
 //                   order (ballot + prefix, no atomics: the order is the list's by construction); then every lane applies the tile's commands.
 //                   A command is expanded into the reference's sequence of internal calls on the fly (a rectangle outline is four lines, a thick
 //                   fast line a polygon and two discs ...), so no expanded list and no per-tile list ever exists in memory: the only scratch is the
@@ -25,6 +28,10 @@
 // Bresenham circle are re-walked by each lane up to its own step, after a tile-level test has let through only the tiles near the line or ring.
 #include "zg_internal.h"
 #include "zg_blend.h"
+// every routine of the canvas kernels is inlined (no calls, so no stack): here the device maths too, which elsewhere is left to the compiler
+#pragma clang attribute push(__attribute__((always_inline)), apply_to = function)
+#include "zg_devmath.h"
+#pragma clang attribute pop
 
 #include <cmath>
 #include <cstring>
@@ -80,14 +87,79 @@ __host__ __device__ __forceinline__ uint32_t cv_spline_fill_points(const float *
     return total;
 }
 
+// ArcRange (:679-750). 2 pi and pi are the reference's comptime values rounded to f32.
+constexpr float CV_TWO_PI = (float)(2.0 * 3.14159265358979323846), CV_PI = (float)3.14159265358979323846;
+constexpr int CV_ARC_MIN_SEGMENTS = 8;
+struct CvArc {
+    float start, end, span; // normalised: start in [0, 2 pi), end in [start, start + 2 pi]
+    bool full, is_long;     // isFull: nothing is gated; isLong: containsCross takes the union of the half-planes
+    int segments;           // drawArcSoft (:889-893)
+    float step;
+};
+__device__ __forceinline__ float cv_arc_normalize(float angle) { // normalize (:697-701); @mod on f32 as the compiler lowers it (unpinned)
+    float n = angle < 0 ? fmodf(fmodf(angle, CV_TWO_PI) + CV_TWO_PI, CV_TWO_PI) : fmodf(angle, CV_TWO_PI);
+    if (n < 0) n += CV_TWO_PI;
+    return n;
+}
+__device__ __forceinline__ CvArc cv_arc_init(float start_angle, float end_angle, float radius) {
+    CvArc a;
+    a.start = cv_arc_normalize(start_angle);
+    a.end = cv_arc_normalize(end_angle);
+    if (a.end < a.start) a.end += CV_TWO_PI;
+    a.span = a.end - a.start;
+    a.full = a.span >= CV_TWO_PI;
+    a.is_long = a.span > CV_PI;
+    const float pieces = ceilf(a.span * radius / 5.0f); // below 2^17 for a radius inside the contract
+    const int s = pieces < (float)CV_BEZIER_MAX_SEGMENTS ? (int)pieces : CV_BEZIER_MAX_SEGMENTS;
+    a.segments = s > CV_ARC_MIN_SEGMENTS ? s : CV_ARC_MIN_SEGMENTS;
+    a.step = a.span / (float)a.segments;
+    return a;
+}
+__device__ __forceinline__ bool cv_arc_contains(const CvArc &a, float angle) { // contains (:706-712): angle is an atan2, in [-pi, pi]
+    const float norm_angle = angle < 0 ? angle + CV_TWO_PI : angle;
+    if (norm_angle >= a.start && norm_angle <= a.end) return true;
+    const float shifted = norm_angle + CV_TWO_PI;
+    return shifted >= a.start && shifted <= a.end;
+}
+__device__ __forceinline__ bool cv_arc_contains_cross(const CvArc &a, float start_cross, float end_cross) { // containsCross (:745-749)
+    const bool s = start_cross <= 0, e = end_cross >= 0;
+    return a.is_long ? (s || e) : (s && e);
+}
+// The sequence v0 = start, v += 1 in f32 (fillArcFast's row walk and its x walk) at its first value whose trunc reaches `target`, with
+// the value before it (-1: there is none; the walks start at 0 or above). Adding 1 is exact inside a binade and rounds only where the
+// sequence crosses a power of two, so it is replayed a binade at a time (tests/canvas_arcs_ref.py: walk_to). disc_fast replays
+// fillCircleFast's row walk the same way in its own loop, left as it is so that the kernel without arcs stays the code it was.
+__device__ __forceinline__ void cv_walk_to(float start, int target, float &v, float &pred) {
+    v = start; pred = -1.0f;
+    for (;;) {
+        const int t = (int)v;
+        if (t >= target) return;
+        if (v < 1.0f) { pred = v; v = v + 1.0f; continue; }
+        const float next_pow2 = __uint_as_float(((__float_as_uint(v) >> 23) + 1u) << 23);
+        const int exact = (int)ceilf(next_pow2 - v) - 1; // steps that stay below it (the difference is exact)
+        const int steps = min(exact, target - t);
+        if (steps > 0) { pred = v + (float)(steps - 1); v = v + (float)steps; }
+        else { pred = v; v = v + 1.0f; }
+    }
+}
+
 // 0: inside the contract; 1: outside it; 2: a polygon or spline polygon of more than ZG_CANVAS_MAX_VERTICES vertices; 3: a filled spline
 // polygon of more than ZG_CANVAS_MAX_CURVE_POINTS points
 __host__ __device__ inline bool cv_coord_ok(float v) { return fabsf(v) <= ZG_CANVAS_MAX_COORD; } // false for NaN and the infinities
 __host__ __device__ inline bool cv_takes_vertices(int kind) { return kind == ZG_DRAW_POLYGON || kind == ZG_DRAW_FILL_POLYGON || kind >= ZG_DRAW_QUAD_BEZIER; }
-__host__ __device__ inline int cv_check(const zg_draw_cmd &c, const float *vertices, uint32_t n_vertices) {
-    const bool known = (c.kind >= ZG_DRAW_LINE && c.kind <= ZG_DRAW_FILL_POLYGON) || (c.kind >= ZG_DRAW_QUAD_BEZIER && c.kind <= ZG_DRAW_FILL_SPLINE_POLYGON);
+// arcs: the caller draws drawArc and fillArc (zg_canvas_draw_arcs and the host form); to zg_canvas_draw they are no kinds
+__host__ __device__ inline bool cv_is_arc(int kind) { return kind == ZG_DRAW_ARC || kind == ZG_DRAW_FILL_ARC; }
+__host__ __device__ inline int cv_check(const zg_draw_cmd &c, const float *vertices, uint32_t n_vertices, bool arcs) {
+    const bool known = (c.kind >= ZG_DRAW_LINE && c.kind <= ZG_DRAW_FILL_POLYGON) || (c.kind >= ZG_DRAW_QUAD_BEZIER && c.kind <= ZG_DRAW_FILL_SPLINE_POLYGON) ||
+                       (arcs && cv_is_arc(c.kind));
     if (!known || (c.mode != ZG_DRAW_FAST && c.mode != ZG_DRAW_SOFT)) return 1;
     if (c.width > ZG_CANVAS_MAX_WIDTH) return 1;
+    if (cv_is_arc(c.kind)) { // the angle pair is one vertex: any value, the non-finite ones draw nothing (:659); centre and radius as a circle's
+        if (c.n_vertices != 1u || c.first_vertex >= n_vertices) return 1;
+        for (int i = 0; i < 3; ++i)
+            if (!cv_coord_ok(c.p[i])) return 1;
+        return 0;
+    }
     if (cv_takes_vertices(c.kind)) {
         if (c.kind == ZG_DRAW_QUAD_BEZIER || c.kind == ZG_DRAW_CUBIC_BEZIER) {
             if (c.n_vertices != (c.kind == ZG_DRAW_QUAD_BEZIER ? 3u : 4u)) return 1;
@@ -120,13 +192,21 @@ __device__ inline float cv_line_pad(float x1, float y1, float x2, float y2, uint
     return pad;
 }
 
+// What an arc can write lies within `pad` of its circle (the disc, for a fill): the ring's half width and the roundings; the soft
+// outline of width 1 is up to 200 Wu lines between points on the circle, with their drift
+__device__ inline float cv_arc_pad(const zg_draw_cmd &c) {
+    if (c.kind == ZG_DRAW_FILL_ARC) return 3.0f;
+    if (c.mode == ZG_DRAW_SOFT && c.width == 1) return cv_line_pad(c.p[0] - c.p[2], c.p[1] - c.p[2], c.p[0] + c.p[2], c.p[1] + c.p[2], 1, ZG_DRAW_SOFT);
+    return 0.5f * (float)c.width + 3.0f;
+}
+
 __global__ __launch_bounds__(256) void k_canvas_prep(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices,
-                                                     uint32_t n_vertices, int rows, int cols, ushort4 *boxes) {
+                                                     uint32_t n_vertices, int rows, int cols, ushort4 *boxes, bool arcs) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t count = count_device ? min(*count_device, n) : n;
     int4 box = make_int4(0, 0, 0, 0);
-    if (i < count && cv_check(cmds[i], vertices, n_vertices) == 0) {
+    if (i < count && cv_check(cmds[i], vertices, n_vertices, arcs) == 0) {
         const zg_draw_cmd c = cmds[i];
         float x0 = 0, y0 = 0, x1 = 0, y1 = 0, pad = 0;
         bool draws = true;
@@ -151,6 +231,14 @@ __global__ __launch_bounds__(256) void k_canvas_prep(const zg_draw_cmd *cmds, ui
             pad = (c.kind == ZG_DRAW_CIRCLE ? 0.5f * (float)c.width : 0.0f) + 3.0f;
             draws = c.p[2] > 0 && (c.kind == ZG_DRAW_FILL_CIRCLE || c.width != 0);
             break;
+        case ZG_DRAW_ARC:
+        case ZG_DRAW_FILL_ARC: { // the circle's box
+            const float a0 = vertices[2 * (size_t)c.first_vertex], a1 = vertices[2 * (size_t)c.first_vertex + 1];
+            x0 = c.p[0] - c.p[2]; x1 = c.p[0] + c.p[2]; y0 = c.p[1] - c.p[2]; y1 = c.p[1] + c.p[2];
+            pad = cv_arc_pad(c);
+            draws = c.p[2] > 0 && (c.kind == ZG_DRAW_FILL_ARC || c.width != 0) && fabsf(a0) < INFINITY && fabsf(a1) < INFINITY;
+            break;
+        }
         default: { // the polygons and the curves: a Bézier stays inside the hull of its control points
             const bool outline = c.kind != ZG_DRAW_FILL_POLYGON && c.kind != ZG_DRAW_FILL_SPLINE_POLYGON;
             const bool spline = c.kind == ZG_DRAW_SPLINE_POLYGON || c.kind == ZG_DRAW_FILL_SPLINE_POLYGON;
@@ -195,8 +283,19 @@ __device__ inline bool cv_far_from_segment(float cx, float cy, float p1x, float 
 // Can the command write into the tile at (tx0, ty0)? Exact "no", generous "yes": for a line the distance from the tile's centre to the
 // segment, for a circle to the ring; the other kinds fill most of their boxes. One lane per command asks this while the tile's list is
 // made; a line or ring that is part of a larger command (an edge of a rectangle or polygon) is asked again by all lanes when it is drawn.
-__device__ inline bool cv_tile_may_touch(const zg_draw_cmd &c, int tx0, int ty0) {
+template <bool ARCS> __device__ inline bool cv_tile_may_touch(const zg_draw_cmd &c, int tx0, int ty0) {
     const float tcx = (float)tx0 + 7.5f, tcy = (float)ty0 + 7.5f;
+    if constexpr (ARCS) {
+        if (cv_is_arc(c.kind)) { // an arc as its ring, a filled arc as its disc
+            const float dx = tcx - c.p[0], dy = tcy - c.p[1], dc = sqrtf(dx * dx + dy * dy), pad = cv_arc_pad(c);
+            if (dc - CV_TILE_REACH > c.p[2] + pad) return false;
+            // The soft outline of width > 1 is a polygon whose inner edge is chords of the circle of radius r - w / 2: at the cap of 200
+            // segments they sag inwards by about r span^2 / 320000, pixels at a radius of tens of thousands, which no fixed pad bounds.
+            // So the polygon has no inner "no"; its chords never leave the outer circle, and poly_fill decides the rest per row.
+            if (c.kind != ZG_DRAW_ARC || (c.mode == ZG_DRAW_SOFT && c.width > 1)) return true;
+            return !(dc + CV_TILE_REACH < c.p[2] - pad);
+        }
+    }
     if (c.kind == ZG_DRAW_LINE)
         return !cv_far_from_segment(tcx, tcy, c.p[0], c.p[1], c.p[2], c.p[3], cv_line_pad(c.p[0], c.p[1], c.p[2], c.p[3], c.width, c.mode) + CV_TILE_REACH + 0.5f);
     if (c.kind == ZG_DRAW_CIRCLE || c.kind == ZG_DRAW_FILL_CIRCLE) {
@@ -270,8 +369,12 @@ template <int PIX> struct Cv {
         if (mode == ZG_DRAW_FAST) solid(color); else pixel(color);
     }
 
-    // renderRing over the full circle (:794-822) with ringBoundingBox and ringCoverage (:754-786)
+    // renderRing (:794-822) with ringBoundingBox and ringCoverage (:754-786). ARC: a pixel the ring covers is written only where the arc
+    // contains its angle (full arcs excepted); without it, the full circle
     __device__ __forceinline__ void ring(float cx, float cy, float inner, float outer, Rgba8 color, int mode) {
+        ring_t<false>(cx, cy, inner, outer, color, mode, CvArc{});
+    }
+    template <bool ARC> __device__ __forceinline__ void ring_t(float cx, float cy, float inner, float outer, Rgba8 color, int mode, const CvArc &arc) {
         const float dc = tile_distance(cx, cy);
         if (dc - CV_TILE_REACH > outer + 3.0f || (inner > 0 && dc + CV_TILE_REACH < inner - 3.0f)) return; // the tile misses the ring
         const int left = (int)roundf(cv_clamp(cx - outer - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - outer - 1, 0.0f, frows));
@@ -289,10 +392,12 @@ template <int PIX> struct Cv {
             if (inner > 0 && dist < inner + 0.5f) alpha = fminf(alpha, dist - (inner - 0.5f));
             const float coverage = cv_clamp(alpha, 0.0f, 1.0f);
             if (coverage <= 0) return;
+            if constexpr (ARC) { if (!arc.full && !cv_arc_contains(arc, dev_atan2f(y, x))) return; }
             pixel(cv_fade(color, coverage));
         } else {
             const bool inside_outer = dist_sq <= outer * outer;
             const bool outside_inner = inner <= 0 || dist_sq >= inner * inner;
+            if constexpr (ARC) { if (inside_outer && outside_inner && !arc.full && !cv_arc_contains(arc, dev_atan2f(y, x))) return; }
             if (inside_outer && outside_inner) solid(color);
         }
     }
@@ -300,7 +405,9 @@ template <int PIX> struct Cv {
     // drawBresenhamCircle over the full circle (:826-860): f32 state that only ever holds integers. The step (x, y) that can reach this
     // pixel is fixed by the pixel (x = the larger, y = the smaller of its |offsets|); the lane walks to it, then makes the step's eight
     // setPoint calls in their order, so a pixel that two of the offsets name (y == 0, x == y) is written twice.
-    __device__ __forceinline__ void circle_bresenham(float center_x, float center_y, float radius, Rgba8 color) {
+    // ARC: each of the eight is gated by the arc containing atan2 of its offset. The offsets are negated f32 values, so an offset of 0
+    // is +0 or -0, and atan2 tells them apart (atan2(0, -0) = pi, atan2(-0, -0) = -pi): the signs decide which axis points an arc keeps.
+    template <bool ARC> __device__ __forceinline__ void circle_bresenham(float center_x, float center_y, float radius, Rgba8 color, const CvArc &arc) {
         const float cx = roundf(center_x), cy = roundf(center_y), r = roundf(radius);
         const float dc = tile_distance(cx, cy);
         if (dc - CV_TILE_REACH > r + 2.0f || dc + CV_TILE_REACH < r - 2.0f) return;
@@ -315,6 +422,16 @@ template <int PIX> struct Cv {
             if (err > 0) { x -= 1; err -= 2 * x + 1; }
         }
         if (!hit) return;
+        if constexpr (ARC) {
+#pragma unroll 1
+            for (int k = 0; k < 8; ++k) { // (x, y) (-x, y) (x, -y) (-x, -y) (y, x) (-y, x) (y, -x) (-y, -x)
+                float o0 = k < 4 ? x : y, o1 = k < 4 ? y : x;
+                if (k & 1) o0 = -o0;
+                if (k & 2) o1 = -o1;
+                if (o0 == ox && o1 == oy && (arc.full || cv_arc_contains(arc, dev_atan2f(o1, o0)))) pixel(color);
+            }
+            return;
+        }
         if (x == ox && y == oy) pixel(color);
         if (-x == ox && y == oy) pixel(color);
         if (x == ox && -y == oy) pixel(color);
@@ -360,6 +477,87 @@ template <int PIX> struct Cv {
         const float y = s_row[3 * (tid >> 4)];
         if (y >= 0) span(s_row[3 * (tid >> 4) + 1], s_row[3 * (tid >> 4) + 2], y, color);
         __syncthreads();
+    }
+
+    // fillArcFast (:1088-1146). Rows: the walk of fillCircleFast, its value for each row of the tile found once by lanes 0-15. Within a
+    // row the reference visits one sequence of x values, v0 = scan_left, v += 1 in f32 (x and span_end both move along it), and joins
+    // consecutive ones that lie in the wedge into spans [v_a, v_b], each stored as pixels floor(v_a) .. ceil(v_b). A value belongs to a
+    // span when it is in the wedge and either not past scan_right (the outer loop starts or continues a span there) or reached by the
+    // inner loop from the value before it (that one short of scan_right and in the wedge, this one inside the circle). Consecutive values
+    // are 1 apart up to a rounding, so the spans' pixels are those of their values, floor(v) .. ceil(v) each: this pixel is stored when a
+    // value of a span lies in (col - 1, col + 1), and at most two values do. The stores are plain, so once is as good as twice.
+    // (tests/canvas_arcs_ref.py: arc_fill_fast_gather, held to the literal loops.) Entered by all lanes together.
+    __device__ __forceinline__ void arc_fill_fast(float cx, float cy, float radius, Rgba8 color, const CvArc &arc) {
+        if (arc.span <= 0) return;
+        if (tile_distance(cx, cy) - CV_TILE_REACH > radius + 3.0f) return;
+        const float top = fmaxf(0.0f, cy - radius), bottom = fminf(frows - 1, cy + radius);
+        if (tid < CV_TILE) {
+            float y, before;
+            cv_walk_to(top, ty0 + tid, y, before);
+            s_row[tid] = (y <= bottom && (int)y == ty0 + tid) ? y : -1.0f;
+        }
+        __syncthreads();
+        const float y = s_row[tid >> 4];
+        __syncthreads();
+        if (!(y >= 0)) return;
+        const float cos_s = dev_cosf(arc.start), sin_s = dev_sinf(arc.start), cos_e = dev_cosf(arc.end), sin_e = dev_sinf(arc.end); // startVector, endVector
+        const float cx_sin_s = cx * sin_s, cx_sin_e = cx * sin_e;
+        const float left = fmaxf(0.0f, cx - radius), right = fminf(fcols - 1, cx + radius);
+        const float radius_sq = radius * radius;
+        const float dy = y - cy, dx_max_sq = radius_sq - dy * dy;
+        if (dx_max_sq <= 0) return;
+        const float dx_max = sqrtf(dx_max_sq);
+        const float scan_left = fmaxf(left, cx - dx_max), scan_right = fminf(right, cx + dx_max);
+        const float start_const = -cx_sin_s - dy * cos_s, end_const = -cx_sin_e - dy * cos_e;
+        float v, before;
+        cv_walk_to(scan_left, col - 1, v, before);
+        bool stored = false;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (v > fx - 1 && v < fx + 1 && cv_arc_contains_cross(arc, v * sin_s + start_const, v * sin_e + end_const)) {
+                bool in_span = v <= scan_right;
+                if (!in_span && before >= 0 && before < scan_right) {
+                    const float dnx = v - cx;
+                    in_span = !(dnx * dnx + dy * dy > radius_sq) && cv_arc_contains_cross(arc, before * sin_s + start_const, before * sin_e + end_const);
+                }
+                stored = stored || in_span;
+            }
+            before = v; v = v + 1.0f;
+        }
+        if (stored) solid(color);
+    }
+
+    // fillArcSoft (:1179-1218) with calculateArcCoverage (:1149-1176)
+    __device__ __forceinline__ void arc_fill_soft(float cx, float cy, float radius, Rgba8 color, const CvArc &arc) {
+        if (tile_distance(cx, cy) - CV_TILE_REACH > radius + 3.0f) return;
+        const int left = (int)roundf(cv_clamp(cx - radius - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - radius - 1, 0.0f, frows));
+        const int right = (int)roundf(cv_clamp(cx + radius + 1, 0.0f, fcols)), bottom = (int)roundf(cv_clamp(cy + radius + 1, 0.0f, frows));
+        if (left >= right || top >= bottom) return;
+        if (col < left || col >= right || row < top || row >= bottom) return;
+        const float y = fy - cy, x = fx - cx;
+        const float dist_sq = x * x + y * y;
+        if (dist_sq > (radius + 1) * (radius + 1)) return;
+        const float cos_s = dev_cosf(arc.start), sin_s = dev_sinf(arc.start), cos_e = dev_cosf(arc.end), sin_e = dev_sinf(arc.end);
+        const bool in_arc = cv_arc_contains(arc, dev_atan2f(y, x));
+        const float start_cross_product = x * sin_s - y * cos_s, end_cross_product = x * sin_e - y * cos_e; // Point.cross
+        const float start_cross = fabsf(start_cross_product), end_cross = fabsf(end_cross_product);
+        const float eps = 1e-5f;
+        const bool near_start = start_cross < 1.0f && start_cross_product < eps, near_end = end_cross < 1.0f && end_cross_product > -eps;
+        if (!in_arc && !near_start && !near_end) return;
+        const float dist = sqrtf(dist_sq);
+        const float circ_coverage = dist <= radius - 1.0f ? 1.0f : (dist < radius + 1.0f ? cv_clamp(radius - dist + 0.5f, 0.0f, 1.0f) : 0.0f);
+        float coverage;
+        if (!in_arc) {
+            float edge_coverage = 0.0f;
+            if (near_start) edge_coverage = fmaxf(edge_coverage, 1.0f - start_cross);
+            if (near_end) edge_coverage = fmaxf(edge_coverage, 1.0f - end_cross);
+            coverage = circ_coverage * edge_coverage;
+        } else {
+            coverage = circ_coverage;
+            if (start_cross < 1.0f && start_cross_product >= -eps) coverage = fminf(coverage, start_cross);
+            if (end_cross < 1.0f && end_cross_product <= eps) coverage = fminf(coverage, end_cross);
+        }
+        if (coverage > 0) pixel(cv_fade(color, coverage));
     }
 
     // fillPolygon (:935-1017) of the n >= 3 vertices in s_vx / s_vy. Lanes 0-15 each take one row of the tile: the intersections in the
@@ -563,11 +761,23 @@ template <int PIX> struct Cv {
     }
     // Every kind that is one fillPolygon over points the lanes put into s_vx / s_vy, through one call of poly_fill: fillPolygon itself
     // (:935-1017) and fillSplinePolygon (:1296-1355), every edge's points one after the other. Entered by all lanes together.
-    __device__ __forceinline__ void filled(const zg_draw_cmd &c, const float *vertices, Rgba8 color) {
+    // ARCS: also the soft arc outline of width > 1 (:909-913), fillArcRing's (:919-927) outer ring from arc.start by +step and inner ring
+    // from arc.end by -step, 2 (segments + 1) <= 402 points.
+    template <bool ARCS> __device__ __forceinline__ void filled(const zg_draw_cmd &c, const float *vertices, Rgba8 color, const CvArc &arc) {
         const float *v = vertices + 2 * (size_t)c.first_vertex;
         int n = (int)c.n_vertices;
         __syncthreads(); // the previous user of s_vx / s_vy has read them
-        if (c.kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
+        if (ARCS && c.kind == ZG_DRAW_ARC) { // never taken, and not compiled in, without the flag
+            const float line_width = (float)c.width;
+            n = 2 * (arc.segments + 1);
+            for (int i = tid; i < n; i += 256) {
+                const bool outer = i <= arc.segments;
+                const float fi = (float)(outer ? i : i - (arc.segments + 1));
+                const float radius = outer ? c.p[2] + line_width / 2.0f : c.p[2] - line_width / 2.0f;
+                const float angle = outer ? arc.start + fi * arc.step : arc.end + fi * -arc.step;
+                s_vx[i] = c.p[0] + radius * dev_cosf(angle); s_vy[i] = c.p[1] + radius * dev_sinf(angle);
+            }
+        } else if (c.kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
             if (n < 3) return;
             int total = 0;
             for (uint32_t i = 0; i < c.n_vertices; ++i) {
@@ -593,14 +803,24 @@ template <int PIX> struct Cv {
     // drawLine itself, drawRectangle (:590-601) and drawPolygon (:579-587) with their end points from the command, and the curves, whose
     // points the lanes evaluate into LDS first — drawBezierTessellated (:1428-1455) for drawQuadraticBezier (:1221-1245) and
     // drawCubicBezier (:1249-1275), and drawSplinePolygon (:1280-1291), one cubic per edge. Entered by all lanes together.
-    __device__ __forceinline__ void outline(const zg_draw_cmd &c, const float *vertices, Rgba8 color) {
+    // ARCS: also the soft arc outline of width 1 (:904-908), segments + 1 <= 201 points of fillArcRing (:919-927) and a line per pair.
+    template <bool ARCS> __device__ __forceinline__ void outline(const zg_draw_cmd &c, const float *vertices, Rgba8 color, const CvArc &arc) {
         const float *v = vertices + 2 * (size_t)c.first_vertex;
-        const bool curve = c.kind >= ZG_DRAW_QUAD_BEZIER, spline = c.kind == ZG_DRAW_SPLINE_POLYGON;
+        const bool arc_points = ARCS && c.kind == ZG_DRAW_ARC;
+        const bool curve = c.kind >= ZG_DRAW_QUAD_BEZIER || arc_points, spline = c.kind == ZG_DRAW_SPLINE_POLYGON;
         if (!c.width || (spline && c.n_vertices < 3)) return;
         const uint32_t curves = spline ? c.n_vertices : 1u;
         for (uint32_t e = 0; e < curves; ++e) {
             uint32_t calls = c.kind == ZG_DRAW_LINE ? 1u : c.kind == ZG_DRAW_RECT ? 4u : c.n_vertices;
-            if (curve) {
+            if (arc_points) { // false, and its branch not compiled in, without the flag
+                __syncthreads(); // the previous user of s_vx / s_vy has read them
+                if (tid <= arc.segments) {
+                    const float angle = arc.start + (float)tid * arc.step;
+                    s_vx[CV_CURVE_BASE + tid] = c.p[0] + c.p[2] * dev_cosf(angle); s_vy[CV_CURVE_BASE + tid] = c.p[1] + c.p[2] * dev_sinf(angle);
+                }
+                __syncthreads();
+                calls = (uint32_t)arc.segments;
+            } else if (curve) {
                 CvPoint p0, p1, p2, p3;
                 int segments;
                 if (spline) cv_spline_edge(v, c.n_vertices, e, c.p[0], p0, p1, p2, p3);
@@ -657,17 +877,43 @@ template <int PIX> struct Cv {
     }
 
     // One command: the reference's public call
-    __device__ __forceinline__ void apply(const zg_draw_cmd &c, const float *vertices) {
+    // ARCS: drawArc (:654-674) and fillArc (:1039-1059) too. What is the same for the whole command — the normalised range, the segment
+    // count — is worked out here, once; an arc then takes the circle's, the lines' or the polygon's route below, so that the large routines
+    // keep one call site each, or one of the two fills of its own.
+    template <bool ARCS> __device__ __forceinline__ void apply(const zg_draw_cmd &c, const float *vertices) {
         Rgba8 color;
         color[0] = c.color[0]; color[1] = c.color[1]; color[2] = c.color[2]; color[3] = c.color[3];
-        const int kind = c.kind;
+        int kind = c.kind;
+        CvArc arc = {};
+        arc.full = true;
+        bool arc_lines = false, arc_polygon = false;
+        if constexpr (ARCS) {
+            if (cv_is_arc(kind)) {
+                const float start_angle = vertices[2 * (size_t)c.first_vertex], end_angle = vertices[2 * (size_t)c.first_vertex + 1];
+                if (!(c.p[2] > 0) || (kind == ZG_DRAW_ARC && !c.width)) return;
+                if (!(fabsf(start_angle) < INFINITY) || !(fabsf(end_angle) < INFINITY)) return;
+                if (fabsf(end_angle - start_angle) >= CV_TWO_PI) {
+                    kind = kind == ZG_DRAW_ARC ? ZG_DRAW_CIRCLE : ZG_DRAW_FILL_CIRCLE;
+                } else {
+                    arc = cv_arc_init(start_angle, end_angle, c.p[2]);
+                    if (kind == ZG_DRAW_FILL_ARC) {
+                        if (c.mode == ZG_DRAW_FAST) arc_fill_fast(c.p[0], c.p[1], c.p[2], color, arc);
+                        else arc_fill_soft(c.p[0], c.p[1], c.p[2], color, arc);
+                        return;
+                    }
+                    if (c.mode == ZG_DRAW_FAST) kind = ZG_DRAW_CIRCLE; // drawArcFast (:879-886): drawCircleFast's two routes, gated
+                    else if (c.width == 1) arc_lines = true;
+                    else arc_polygon = true;
+                }
+            }
+        }
         if (kind == ZG_DRAW_LINE || kind == ZG_DRAW_RECT || kind == ZG_DRAW_POLYGON || kind == ZG_DRAW_QUAD_BEZIER || kind == ZG_DRAW_CUBIC_BEZIER ||
-            kind == ZG_DRAW_SPLINE_POLYGON) {
-            outline(c, vertices, color);
+            kind == ZG_DRAW_SPLINE_POLYGON || arc_lines) {
+            outline<ARCS>(c, vertices, color, arc);
             return;
         }
-        if (kind == ZG_DRAW_FILL_POLYGON || kind == ZG_DRAW_FILL_SPLINE_POLYGON) {
-            filled(c, vertices, color);
+        if (kind == ZG_DRAW_FILL_POLYGON || kind == ZG_DRAW_FILL_SPLINE_POLYGON || arc_polygon) {
+            filled<ARCS>(c, vertices, color, arc);
             return;
         }
         switch (kind) {
@@ -676,9 +922,9 @@ template <int PIX> struct Cv {
             break;
         case ZG_DRAW_CIRCLE: { // :636-644, :863-876
             if (!(c.p[2] > 0) || !c.width) break;
-            if (c.mode == ZG_DRAW_FAST && c.width == 1) { circle_bresenham(c.p[0], c.p[1], c.p[2], color); break; }
+            if (c.mode == ZG_DRAW_FAST && c.width == 1) { circle_bresenham<ARCS>(c.p[0], c.p[1], c.p[2], color, arc); break; }
             const float line_width = (float)c.width;
-            ring(c.p[0], c.p[1], c.p[2] - line_width / 2.0f, c.p[2] + line_width / 2.0f, color, c.mode);
+            ring_t<ARCS>(c.p[0], c.p[1], c.p[2] - line_width / 2.0f, c.p[2] + line_width / 2.0f, color, c.mode, arc);
             break;
         }
         case ZG_DRAW_FILL_CIRCLE: // :1021-1029
@@ -690,7 +936,7 @@ template <int PIX> struct Cv {
     }
 };
 
-template <int PIX>
+template <int PIX, bool ARCS>
 __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, const ushort4 *boxes) {
     using P = Px<PIX>;
     __shared__ uint16_t s_list[CV_CHUNK];
@@ -722,7 +968,7 @@ __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmd
             if (i < n) {
                 const ushort4 b = boxes[i];
                 hit[j] = (int)b.x < cv.tx0 + CV_TILE && (int)b.z > cv.tx0 && (int)b.y < cv.ty0 + CV_TILE && (int)b.w > cv.ty0;
-                if (hit[j]) hit[j] = cv_tile_may_touch(cmds[i], cv.tx0, cv.ty0); // lines and circles: the box is mostly empty
+                if (hit[j]) hit[j] = cv_tile_may_touch<ARCS>(cmds[i], cv.tx0, cv.ty0); // lines and circles: the box is mostly empty
             }
             ballot[j] = __ballot(hit[j]);
             if (lane == 0) s_wave_count[4 * j + wave] = __popcll(ballot[j]);
@@ -746,7 +992,7 @@ __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmd
         }
         for (int k = 0; k < total; ++k) {
             const uint32_t ci = base + (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[k]);
-            cv.apply(cmds[ci], vertices);
+            cv.template apply<ARCS>(cmds[ci], vertices);
         }
         __syncthreads();
     }
@@ -782,8 +1028,15 @@ static int check_canvas_image(const zg_image *img, bool device_pointer) {
     return ZG_OK;
 }
 
+template <int PIX> static void launch_canvas(bool arcs, dim3 grid, hipStream_t s, DImg d, const zg_draw_cmd *cmds, uint32_t n, const float *vertices,
+                                             const ushort4 *boxes) {
+    if (arcs) k_canvas<PIX, true><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
+    else k_canvas<PIX, false><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
+}
+
+// arcs: the kernel that knows drawArc and fillArc; without it they are skipped as no kinds
 static int canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
-                       hipStream_t s) {
+                       hipStream_t s, bool arcs) {
     ZG_REQUIRE(n <= ZG_CANVAS_MAX_COMMANDS, ZG_ERR_UNSUPPORTED, "canvas_draw: %u commands (at most %u a call)", n, ZG_CANVAS_MAX_COMMANDS);
     if (n == 0 || img->rows == 0 || img->cols == 0) return ZG_OK;
     ScratchBlock sc(s);
@@ -791,16 +1044,16 @@ static int canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n,
     sc.take(boxes, n);
     int rc;
     if ((rc = sc.alloc())) return rc;
-    k_canvas_prep<<<ceil_div(n, 256), 256, 0, s>>>(cmds, n, count_device, vertices, n_vertices, (int)img->rows, (int)img->cols, boxes);
+    k_canvas_prep<<<ceil_div(n, 256), 256, 0, s>>>(cmds, n, count_device, vertices, n_vertices, (int)img->rows, (int)img->cols, boxes, arcs);
     if ((rc = launch_ok("k_canvas_prep"))) return rc;
     const dim3 grid(ceil_div(img->cols, CV_TILE), ceil_div(img->rows, CV_TILE));
     const DImg d = dimg(img);
     switch (img->pixel) {
-    case ZG_PIXEL_U8: k_canvas<ZG_PIXEL_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
-    case ZG_PIXEL_RGB_U8: k_canvas<ZG_PIXEL_RGB_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
-    default: k_canvas<ZG_PIXEL_RGBA_U8><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes); break;
+    case ZG_PIXEL_U8: launch_canvas<ZG_PIXEL_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
+    case ZG_PIXEL_RGB_U8: launch_canvas<ZG_PIXEL_RGB_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
+    default: launch_canvas<ZG_PIXEL_RGBA_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
     }
-    return launch_ok("k_canvas");
+    return launch_ok(arcs ? "k_canvas (arcs)" : "k_canvas");
 }
 
 static int check_builder(const uint32_t *count, const uint8_t *color, uint32_t width, int mode, const uint32_t *count_out, const char *what) {
@@ -824,15 +1077,25 @@ int zg_canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, con
     if (const int rc = check_canvas_image(img, true)) return rc;
     ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
     ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
-    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream));
+    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), false);
+}
+
+int zg_canvas_draw_arcs(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
+                        zg_stream stream) {
+    if (const int rc = check_canvas_image(img, true)) return rc;
+    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_arcs: null cmds");
+    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_arcs: null vertices");
+    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), true);
 }
 
 int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, uint32_t n_vertices) {
     if (const int rc = check_canvas_image(img, false)) return rc;
     ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
     ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
+    bool arcs = false; // the host sees the list: the larger kernel only when it holds an arc
     for (uint32_t i = 0; i < n; ++i) {
-        const int bad = cv_check(cmds[i], vertices, n_vertices);
+        const int bad = cv_check(cmds[i], vertices, n_vertices, true);
+        arcs = arcs || cv_is_arc(cmds[i].kind);
         ZG_REQUIRE(bad != 2, ZG_ERR_UNSUPPORTED, "canvas_draw: command %u is a polygon of %u vertices (at most %u)", i, cmds[i].n_vertices, ZG_CANVAS_MAX_VERTICES);
         ZG_REQUIRE(bad != 3, ZG_ERR_UNSUPPORTED, "canvas_draw: command %u is a filled spline polygon of more than %u points", i, ZG_CANVAS_MAX_CURVE_POINTS);
         ZG_REQUIRE(bad == 0, ZG_ERR_INVALID_ARGUMENT,
@@ -849,7 +1112,7 @@ int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n
     if ((rc = sc.alloc())) return rc;
     if ((rc = upload_pageable(dcmds, cmds, (size_t)n * sizeof(zg_draw_cmd), nullptr))) return rc;
     if (n_vertices && (rc = upload_pageable(dvertices, vertices, 2 * (size_t)n_vertices * sizeof(float), nullptr))) return rc;
-    return host_in_place(img, true, [&](const zg_image *d) { return canvas_draw(d, dcmds, n, nullptr, dvertices, n_vertices, nullptr); });
+    return host_in_place(img, true, [&](const zg_image *d) { return canvas_draw(d, dcmds, n, nullptr, dvertices, n_vertices, nullptr, arcs); });
 }
 
 int zg_canvas_cmds_from_hough_lines(const zg_hough_line *lines, const uint32_t *counts, uint32_t capacity, const uint8_t *color, uint32_t width, int mode,
