@@ -751,4 +751,8 @@ ZG_API void zg_jpeg_free(void *p);
  * its own in the same way (_CANVAS_SIGNATURES, zig/zignal_hip_canvas.zig). */
 #include "zignal_hip_canvas.h"
 
+/* Canvas(T).drawText with a caller-supplied BitmapFont (src/canvas/Canvas.zig:1476-1658, src/font/BitmapFont.zig): a module of its own in
+ * the same way (_TEXT_SIGNATURES, zig/zignal_hip_text.zig). */
+#include "zignal_hip_text.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -149,6 +149,27 @@ CANVAS_MAX_VERTICES, CANVAS_MAX_COORD, CANVAS_MAX_WIDTH, CANVAS_MAX_SIZE, CANVAS
 CANVAS_MAX_CURVE_POINTS = 512
 
 
+class ZgGlyph(C.Structure):
+    """zg_glyph: one entry of a variable-width font's glyph table (include/zignal_hip_text.h). 16 bytes."""
+    _fields_ = [("codepoint", C.c_uint32), ("bitmap_offset", C.c_uint32), ("width", C.c_uint8), ("height", C.c_uint8), ("x_offset", C.c_int16),
+                ("y_offset", C.c_int16), ("device_width", C.c_int16)]
+
+
+class ZgFont(C.Structure):
+    """zg_font: a BitmapFont by value; data and glyphs are host or device addresses, as the call takes them. 32 bytes."""
+    _fields_ = [("data", C.c_void_p), ("glyphs", C.c_void_p), ("data_len", C.c_uint32), ("n_glyphs", C.c_uint32), ("char_width", C.c_uint8),
+                ("char_height", C.c_uint8), ("first_char", C.c_uint8), ("last_char", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+class ZgTextCmd(C.Structure):
+    """zg_text_cmd: one drawText call. 28 bytes."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("scale", C.c_float), ("mode", C.c_int32), ("color", C.c_uint8 * 4),
+                ("first_codepoint", C.c_uint32), ("n_codepoints", C.c_uint32)]
+
+
+TEXT_MAX_SCALE, TEXT_MAX_CODEPOINTS, TEXT_MAX_COMMANDS, TEXT_MAX_TOTAL = 64.0, 65536, 65536, 1 << 24  # ZG_TEXT_MAX_*
+
+
 class ZgMetricResult(C.Structure):
     """zg_metric_result: the left-to-right f64 sum, the number of terms, the metric's value and how many terms were added serially."""
     _fields_ = [("sum", C.c_double), ("count", C.c_uint64), ("value", C.c_double), ("serial_terms", C.c_uint64)]
@@ -459,6 +480,22 @@ _CANVAS_SIGNATURES = {
 _CANVAS_RESTYPES = {"zg_sizeof_draw_cmd": C.c_size_t, "zg_canvas_tile": C.c_uint32}
 CANVAS_EXPORTED_SYMBOLS = tuple(_CANVAS_SIGNATURES)
 
+# the text module: every symbol include/zignal_hip_text.h declares
+_FONT = C.POINTER(ZgFont)
+_TEXT_SIGNATURES = {
+    "zg_sizeof_font": [],
+    "zg_sizeof_glyph": [],
+    "zg_sizeof_text_cmd": [],
+    "zg_font_check": [_FONT],
+    "zg_font_upload": [_FONT, _FONT],
+    "zg_font_free": [_FONT],
+    "zg_text_bounds_host": [_FONT, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_float)],
+    "zg_canvas_draw_text": [_IMG, _FONT, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "zg_canvas_draw_text_host": [_IMG, _FONT, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32],
+}
+_TEXT_RESTYPES = {"zg_sizeof_font": C.c_size_t, "zg_sizeof_glyph": C.c_size_t, "zg_sizeof_text_cmd": C.c_size_t}
+TEXT_EXPORTED_SYMBOLS = tuple(_TEXT_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -470,7 +507,8 @@ def lib() -> C.CDLL:
         l = C.CDLL(LIB_PATH)
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
-                                (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES)):
+                                (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
+                                (_TEXT_SIGNATURES, _TEXT_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes
@@ -479,6 +517,9 @@ def lib() -> C.CDLL:
             raise ImportError(f"{LIB_PATH}: sizeof(zg_step) is {l.zg_sizeof_step()} in the library, {C.sizeof(ZgStep)} in this binding: rebuild the library")
         if l.zg_sizeof_draw_cmd() != C.sizeof(ZgDrawCmd):  # the same rule for zg_draw_cmd arrays
             raise ImportError(f"{LIB_PATH}: sizeof(zg_draw_cmd) is {l.zg_sizeof_draw_cmd()} in the library, {C.sizeof(ZgDrawCmd)} in this binding: rebuild the library")
+        for name, struct in (("zg_sizeof_font", ZgFont), ("zg_sizeof_glyph", ZgGlyph), ("zg_sizeof_text_cmd", ZgTextCmd)):  # and for the text module's three
+            if getattr(l, name)() != C.sizeof(struct):
+                raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
         _lib = l
     return _lib
 

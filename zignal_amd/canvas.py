@@ -205,13 +205,59 @@ class Canvas:
         """The pie slice between the two angles (see draw_arc)."""
         return self._add(L.DRAW_FILL_ARC, color, 1, mode, (center[0], center[1], radius), pts=((start_angle, end_angle),))
 
+    def draw_text(self, text, position, color, font, scale: float = 1.0, mode="fast"):
+        """drawText: `text` (a str, decoded to its codepoints; "\\n" starts a new line) with its top left corner at `position`, in a
+        zg.BitmapFont. scale == 1 lights the glyphs' bits in either mode; otherwise "fast" writes a block per bit and "soft" box-filtered
+        coverage. scale <= 0 draws nothing; scale at most TEXT_MAX_SCALE."""
+        from .text import codepoints_of
+
+        self.commands.append({"text": codepoints_of(text), "x": float(position[0]), "y": float(position[1]), "scale": float(scale), "mode": _mode(mode),
+                              "color": _color(color), "font": font})
+        return self
+
     def flush(self, stream=None) -> None:
         """Draw the list and empty it. Device image: the two lists are uploaded (one synchronous copy each) and zg_canvas_draw — or
         zg_canvas_draw_arcs when the list holds an arc — runs on `stream` (a torch stream; default: the current one). Host image:
-        zg_canvas_draw_host."""
+        zg_canvas_draw_host. A list with text in it is cut into maximal runs of text and of everything else, issued in list order on the one
+        stream: the others as above, a run of text through zg_canvas_draw_text (host image: zg_canvas_draw_text_host), one call per font."""
         commands, self.commands = self.commands, []
         if not commands:
             return
+        if not any("text" in c for c in commands):
+            self._flush_shapes(commands, stream)
+            return
+        run = []
+        for c in commands + [None]:
+            if run and (c is None or ("text" in c) != ("text" in run[0]) or ("text" in c and c["font"] is not run[0]["font"])):
+                if "text" in run[0]:
+                    self._flush_text(run, stream)
+                else:
+                    self._flush_shapes(run, stream)
+                run = []
+            run.append(c)
+
+    def _flush_text(self, commands, stream) -> None:
+        from . import text as T
+
+        font = commands[0]["font"]
+        cmds, cps = T.pack_text(commands)
+        if not self.image.on_device:
+            T.draw_text_host(self.image, font, cmds, cps)
+            return
+        if not len(cps):
+            return
+        dev = self.image.data.device
+        dcmds = torch.from_numpy(cmds.view(np.uint8)).to(dev)
+        dcps = torch.from_numpy(cps.view(np.int32)).to(dev)
+        if stream is None:
+            T.draw_text(self.image, font, dcmds, dcps)
+        else:
+            with torch.cuda.stream(stream):
+                T.draw_text(self.image, font, dcmds, dcps)
+            dcmds.record_stream(stream)
+            dcps.record_stream(stream)
+
+    def _flush_shapes(self, commands, stream) -> None:
         cmds, vertices = pack_commands(commands)
         if not self.image.on_device:
             draw_host(self.image, cmds, vertices)

@@ -967,6 +967,91 @@ inline void HoughTransform::computeInto(const DeviceImage<uint8_t> &edges, const
 // ---- canvas: Canvas(T) (src/canvas/Canvas.zig) ----
 enum class DrawMode { fast = ZG_DRAW_FAST, soft = ZG_DRAW_SOFT };                         // Canvas.zig:19-24
 struct Point2 { float x, y; };
+// BitmapFont (src/font/BitmapFont.zig) with the caller's glyph data, in the reference's two forms; checked when made (zg_font_check) and
+// uploaded to the current device on first use there. The library ships no glyphs.
+inline std::vector<uint32_t> decodeUtf8(const std::string &s) {
+    std::vector<uint32_t> out;
+    for (size_t i = 0; i < s.size();) {
+        const uint8_t b = (uint8_t)s[i];
+        const int extra = b < 0x80 ? 0 : (b >> 5) == 6 ? 1 : (b >> 4) == 14 ? 2 : (b >> 3) == 30 ? 3 : -1;
+        if (extra < 0 || i + (size_t)extra >= s.size() + (extra ? 0 : 1)) throw Error(ZG_ERR_INVALID_ARGUMENT, "decodeUtf8: invalid UTF-8");
+        uint32_t cp = extra == 0 ? b : (uint32_t)(b & (0x3F >> extra));
+        for (int k = 1; k <= extra; ++k) {
+            const uint8_t c = (uint8_t)s[i + (size_t)k];
+            if ((c >> 6) != 2) throw Error(ZG_ERR_INVALID_ARGUMENT, "decodeUtf8: invalid UTF-8");
+            cp = (cp << 6) | (c & 0x3Fu);
+        }
+        out.push_back(cp);
+        i += (size_t)extra + 1;
+    }
+    return out;
+}
+class BitmapFont {
+  public:
+    // glyph c is char_height rows of (char_width + 7) / 8 bytes at (c - first_char) times that, bits LSB first; the font ends with the last whole glyph of data
+    static BitmapFont fromFixed(uint8_t char_width, uint8_t char_height, uint8_t first_char, std::vector<uint8_t> data) {
+        const size_t per_char = (size_t)char_height * (((size_t)char_width + 7) / 8), count = per_char ? data.size() / per_char : 0;
+        if (count < 1) throw Error(ZG_ERR_INVALID_ARGUMENT, "BitmapFont::fromFixed: no whole glyph in data");
+        BitmapFont f;
+        f.meta_.char_width = char_width; f.meta_.char_height = char_height; f.meta_.first_char = first_char;
+        f.meta_.last_char = (uint8_t)std::min<size_t>(255, (size_t)first_char + count - 1);
+        f.data_ = std::move(data);
+        f.checked();
+        return f;
+    }
+    // the glyph table (sorted by codepoint here); a line is char_height high, a codepoint the table lacks advances by char_width
+    static BitmapFont fromGlyphs(uint8_t char_height, std::vector<zg_glyph> glyphs, std::vector<uint8_t> data, uint8_t char_width) {
+        BitmapFont f;
+        f.meta_.char_width = char_width; f.meta_.char_height = char_height;
+        std::stable_sort(glyphs.begin(), glyphs.end(), [](const zg_glyph &a, const zg_glyph &b) { return a.codepoint < b.codepoint; });
+        f.glyphs_ = std::move(glyphs);
+        f.table_ = true;
+        f.data_ = std::move(data);
+        f.checked();
+        return f;
+    }
+    BitmapFont(BitmapFont &&o) noexcept : meta_(o.meta_), data_(std::move(o.data_)), glyphs_(std::move(o.glyphs_)), table_(o.table_), device_(o.device_) { o.device_ = zg_font{}; }
+    BitmapFont(const BitmapFont &) = delete;
+    BitmapFont &operator=(const BitmapFont &) = delete;
+    ~BitmapFont() { (void)zg_font_free(&device_); }
+    zg_font host() const {
+        zg_font f = meta_;
+        f.data = data_.data(); f.data_len = (uint32_t)data_.size();
+        f.glyphs = table_ ? (glyphs_.empty() ? &no_glyph_ : glyphs_.data()) : nullptr; f.n_glyphs = (uint32_t)glyphs_.size();
+        return f;
+    }
+    const zg_font &device() const { // uploaded on first use
+        if (device_.data == nullptr) {
+            const zg_font h = host();
+            check(zg_font_upload(&h, &device_));
+        }
+        return device_;
+    }
+    // getTextBounds: l = t = 0, r and b exclusive
+    Rectangle<float> textBounds(const std::string &utf8, float scale = 1.0f) const {
+        const std::vector<uint32_t> cps = decodeUtf8(utf8);
+        const zg_font h = host();
+        float ltrb[4];
+        check(zg_text_bounds_host(&h, cps.data(), (uint32_t)cps.size(), scale, ltrb));
+        return Rectangle<float>{ltrb[0], ltrb[1], ltrb[2], ltrb[3]};
+    }
+
+  private:
+    BitmapFont() = default;
+    void checked() const {
+        if (zg_sizeof_font() != sizeof(zg_font) || zg_sizeof_glyph() != sizeof(zg_glyph) || zg_sizeof_text_cmd() != sizeof(zg_text_cmd)) // the zg_sizeof_step rule
+            throw Error(ZG_ERR_INVALID_ARGUMENT, "libzignal_hip: zg_font, zg_glyph or zg_text_cmd has another size in the library than in this header");
+        const zg_font h = host();
+        check(zg_font_check(&h));
+    }
+    zg_font meta_{};
+    std::vector<uint8_t> data_;
+    std::vector<zg_glyph> glyphs_;
+    bool table_ = false;
+    zg_glyph no_glyph_{};
+    mutable zg_font device_{};
+};
+
 // Canvas(T) over an Image<T> or DeviceImage<T> of u8, Rgb<uint8_t> or Rgba<uint8_t>: the draw methods (lines, rectangles, circles, arcs,
 // polygons, Bézier curves, spline polygons) append to a command list, flush()
 // executes it into the image in list order (zg_canvas_draw_host for host pixels; for device pixels the two lists are uploaded and
@@ -1020,12 +1105,82 @@ template <typename T, template <class> class Img = Image> class Canvas {
     Canvas &fillSplinePolygon(const std::vector<Point2> &polygon, Rgba<uint8_t> color, float tension, DrawMode mode = DrawMode::fast) {
         return addPolygon(ZG_DRAW_FILL_SPLINE_POLYGON, polygon, mode, 1, color, tension);
     }
+    // drawText: UTF-8 text ('\n' starts a new line) with its top left corner at `position`. scale == 1 lights the glyphs' bits in either mode;
+    // otherwise .fast writes a block per bit and .soft box-filtered coverage. The font must outlive flush().
+    Canvas &drawText(const std::string &utf8, Point2 position, Rgba<uint8_t> color, const BitmapFont &font, float scale = 1.0f, DrawMode mode = DrawMode::fast) {
+        TextItem t{};
+        t.cmd.x = position.x; t.cmd.y = position.y; t.cmd.scale = scale; t.cmd.mode = (int32_t)mode;
+        t.cmd.color[0] = color.r; t.cmd.color[1] = color.g; t.cmd.color[2] = color.b; t.cmd.color[3] = color.a;
+        t.codepoints = decodeUtf8(utf8);
+        t.font = &font;
+        t.after = cmds_.size();
+        texts_.push_back(std::move(t));
+        return *this;
+    }
     const std::vector<zg_draw_cmd> &commands() const { return cmds_; }
+    // A list with text in it is cut into maximal runs of text and of everything else, issued in list order: the others through
+    // zg_canvas_draw (or _arcs, or _host), a run of text through zg_canvas_draw_text (or _host), one call per font.
     void flush() {
         std::vector<zg_draw_cmd> cmds;
         std::vector<float> vertices;
+        std::vector<TextItem> texts;
         cmds.swap(cmds_);
         vertices.swap(vertices_);
+        texts.swap(texts_);
+        size_t done = 0;
+        for (size_t i = 0; i < texts.size();) {
+            if (texts[i].after > done) flushShapes(cmds.data() + done, texts[i].after - done, vertices);
+            done = texts[i].after;
+            size_t j = i + 1;
+            while (j < texts.size() && texts[j].after == done && texts[j].font == texts[i].font) ++j;
+            flushText(texts.data() + i, j - i);
+            i = j;
+        }
+        if (cmds.size() > done) flushShapes(cmds.data() + done, cmds.size() - done, vertices);
+    }
+    // the device-list form of drawText: every pointer is device memory (the font's through font.device()); asynchronous, recordable into a graph
+    void drawTexts(const BitmapFont &font, const zg_text_cmd *cmds, uint32_t n, const uint32_t *codepoints, uint32_t n_codepoints, const uint32_t *count_device = nullptr) const {
+        const zg_image d = image_->desc();
+        check(zg_canvas_draw_text(&d, &font.device(), cmds, n, count_device, codepoints, n_codepoints, image_->stream()));
+    }
+
+  private:
+    struct TextItem {
+        zg_text_cmd cmd;
+        std::vector<uint32_t> codepoints;
+        const BitmapFont *font;
+        size_t after; // the number of other commands issued before it
+    };
+    void flushText(const TextItem *items, size_t count) {
+        std::vector<zg_text_cmd> cmds;
+        std::vector<uint32_t> cps;
+        for (size_t k = 0; k < count; ++k) {
+            zg_text_cmd c = items[k].cmd;
+            c.first_codepoint = (uint32_t)cps.size(); c.n_codepoints = (uint32_t)items[k].codepoints.size();
+            cps.insert(cps.end(), items[k].codepoints.begin(), items[k].codepoints.end());
+            cmds.push_back(c);
+        }
+        const zg_image d = image_->desc();
+        const uint32_t n = (uint32_t)cmds.size(), ncp = (uint32_t)cps.size();
+        if constexpr (!Img<T>::on_device) {
+            const zg_font h = items[0].font->host();
+            check(zg_canvas_draw_text_host(&d, &h, cmds.data(), n, ncp ? cps.data() : nullptr, ncp));
+        } else {
+            if (ncp == 0) return;
+            const zg_font &f = items[0].font->device();
+            void *mem = nullptr;
+            const size_t cmd_bytes = (cmds.size() * sizeof(zg_text_cmd) + 255) / 256 * 256;
+            check(zg_malloc(&mem, cmd_bytes + cps.size() * sizeof(uint32_t) + 256));
+            int rc = zg_memcpy_h2d(mem, cmds.data(), cmds.size() * sizeof(zg_text_cmd), image_->stream());
+            if (!rc) rc = zg_memcpy_h2d((char *)mem + cmd_bytes, cps.data(), cps.size() * sizeof(uint32_t), image_->stream());
+            if (!rc) rc = zg_canvas_draw_text(&d, &f, (const zg_text_cmd *)mem, n, nullptr, (const uint32_t *)((char *)mem + cmd_bytes), ncp, image_->stream());
+            (void)zg_free(mem); // waits for the draw that reads the lists
+            check(rc);
+        }
+    }
+    // `count` commands of the list; their vertex ranges index the whole vertex array
+    void flushShapes(const zg_draw_cmd *cmds_at, size_t count, const std::vector<float> &vertices) {
+        const std::vector<zg_draw_cmd> cmds(cmds_at, cmds_at + count);
         if (cmds.empty()) return;
         const zg_image d = image_->desc();
         const uint32_t n = (uint32_t)cmds.size(), nv = (uint32_t)(vertices.size() / 2);
@@ -1044,6 +1199,8 @@ template <typename T, template <class> class Img = Image> class Canvas {
             check(rc);
         }
     }
+
+  public:
     // the device-list form: every pointer is device memory; asynchronous, nothing is synchronised, recordable into a graph
     // arcs: zg_canvas_draw_arcs, for a list that may hold ZG_DRAW_ARC or ZG_DRAW_FILL_ARC (zg_canvas_draw skips them)
     void draw(const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device = nullptr, const float *vertices = nullptr, uint32_t n_vertices = 0,
@@ -1078,6 +1235,7 @@ template <typename T, template <class> class Img = Image> class Canvas {
     const Img<T> *image_;
     std::vector<zg_draw_cmd> cmds_;
     std::vector<float> vertices_;
+    std::vector<TextItem> texts_;
 };
 
 } // namespace zignal
