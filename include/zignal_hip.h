@@ -755,4 +755,8 @@ ZG_API void zg_jpeg_free(void *p);
  * the same way (_TEXT_SIGNATURES, zig/zignal_hip_text.zig). */
 #include "zignal_hip_text.h"
 
+/* FeatureDistributionMatching(T) (src/fdm.zig): integer moments, the reference's SVD and products, the per-pixel map, and the chains over
+ * them: a module of its own in the same way (_FDM_SIGNATURES, zig/zignal_hip_fdm.zig). */
+#include "zignal_hip_fdm.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -180,6 +180,28 @@ class ZgMetricOptions(C.Structure):
     _fields_ = [("ssim_window", C.c_void_p), ("ssim_map", C.c_void_p)]
 
 
+class ZgFdmMoments(C.Structure):
+    """zg_fdm_moments: the exact integer moments of one frame (include/zignal_hip_fdm.h). 104 bytes."""
+    _fields_ = [("n", C.c_uint64), ("sum", C.c_uint64 * 3), ("prod", C.c_uint64 * 6), ("lum_sum", C.c_uint64), ("lum_sq", C.c_uint64),
+                ("not_gray", C.c_uint32), ("pixel", C.c_int32)]
+
+
+class ZgFdmTarget(C.Structure):
+    """zg_fdm_target: what setTarget keeps (fdm.zig:29-32). 136 bytes."""
+    _fields_ = [("mean", C.c_double * 3), ("u", C.c_double * 9), ("s", C.c_double * 3), ("is_gray", C.c_int32), ("status", C.c_int32),
+                ("pixel", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ZgFdmTransform(C.Structure):
+    """zg_fdm_transform: what update applies to every pixel. 120 bytes."""
+    _fields_ = [("route", C.c_int32), ("status", C.c_int32), ("w", C.c_double * 9), ("bias", C.c_double * 3), ("scale", C.c_double),
+                ("offset", C.c_double)]
+
+
+FDM_ROUTE_COLOR, FDM_ROUTE_SCALAR, FDM_ROUTE_GRAY_TARGET = range(3)
+FDM_STATUS_TYPE_MISMATCH = -1
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -496,6 +518,33 @@ _TEXT_SIGNATURES = {
 _TEXT_RESTYPES = {"zg_sizeof_font": C.c_size_t, "zg_sizeof_glyph": C.c_size_t, "zg_sizeof_text_cmd": C.c_size_t}
 TEXT_EXPORTED_SYMBOLS = tuple(_TEXT_SIGNATURES)
 
+# the feature-distribution-matching module: every symbol include/zignal_hip_fdm.h declares
+_FDM_M, _FDM_T, _FDM_X = C.POINTER(ZgFdmMoments), C.POINTER(ZgFdmTarget), C.POINTER(ZgFdmTransform)
+_FDM_SIGNATURES = {
+    "zg_fdm_sizeof_moments": [],
+    "zg_fdm_sizeof_target": [],
+    "zg_fdm_sizeof_transform": [],
+    "zg_fdm_lane_run": [],
+    "zg_fdm_frames_per_launch": [],
+    "zg_fdm_compute_moments": [_IMG, C.c_void_p, C.c_void_p],
+    "zg_fdm_compute_moments_frames": [_IMG, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_fdm_target_from_moments": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_fdm_transform_from_moments": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_fdm_transform_from_moments_frames": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_fdm_target_host": [C.c_int, _F64P, _F64P, C.c_int, _FDM_T],
+    "zg_fdm_transform_host": [C.c_int, _FDM_T, _F64P, _F64P, _FDM_X],
+    "zg_fdm_stats_from_moments_host": [_FDM_M, C.c_int, _F64P, _F64P],
+    "zg_fdm_apply": [_IMG, C.c_void_p, C.c_void_p],
+    "zg_fdm_apply_frames": [_IMG, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_fdm_match": [_IMG, _IMG, C.c_void_p],
+    "zg_fdm_match_frames": [_IMG, C.c_uint32, _IMG, C.c_void_p, C.c_void_p],
+    "zg_fdm_match_host": [_IMG, _IMG],
+    "zg_fdm_match_frames_host": [_IMG, C.c_uint32, _IMG],
+}
+_FDM_RESTYPES = {"zg_fdm_sizeof_moments": C.c_size_t, "zg_fdm_sizeof_target": C.c_size_t, "zg_fdm_sizeof_transform": C.c_size_t,
+                 "zg_fdm_lane_run": C.c_uint32, "zg_fdm_frames_per_launch": C.c_uint32}
+FDM_EXPORTED_SYMBOLS = tuple(_FDM_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -508,7 +557,7 @@ def lib() -> C.CDLL:
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
                                 (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
-                                (_TEXT_SIGNATURES, _TEXT_RESTYPES)):
+                                (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes
@@ -518,6 +567,9 @@ def lib() -> C.CDLL:
         if l.zg_sizeof_draw_cmd() != C.sizeof(ZgDrawCmd):  # the same rule for zg_draw_cmd arrays
             raise ImportError(f"{LIB_PATH}: sizeof(zg_draw_cmd) is {l.zg_sizeof_draw_cmd()} in the library, {C.sizeof(ZgDrawCmd)} in this binding: rebuild the library")
         for name, struct in (("zg_sizeof_font", ZgFont), ("zg_sizeof_glyph", ZgGlyph), ("zg_sizeof_text_cmd", ZgTextCmd)):  # and for the text module's three
+            if getattr(l, name)() != C.sizeof(struct):
+                raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
+        for name, struct in (("zg_fdm_sizeof_moments", ZgFdmMoments), ("zg_fdm_sizeof_target", ZgFdmTarget), ("zg_fdm_sizeof_transform", ZgFdmTransform)):
             if getattr(l, name)() != C.sizeof(struct):
                 raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
         _lib = l

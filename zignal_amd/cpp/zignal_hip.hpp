@@ -1238,4 +1238,65 @@ template <typename T, template <class> class Img = Image> class Canvas {
     std::vector<TextItem> texts_;
 };
 
+// FeatureDistributionMatching(T) (src/fdm.zig:19-274) for T = uint8_t, Rgb<uint8_t>, Rgba<uint8_t>: setTarget once, then setSource and
+// update for every frame; the source is matched in place. Over Image (the default) every update stages source and target and is
+// synchronous (zg_fdm_match_host); over DeviceImage setTarget leaves the target's statistics in device memory and update enqueues moments,
+// transform and apply on the source's stream with nothing copied or synchronised (zg_fdm_match_frames). The images are borrowed: they
+// outlive the calls that use them. The statistics come from exact integer moments, not from the reference's Welford recurrence
+// (include/zignal_hip_fdm.h says what that can change: a byte whose value before rounding is a tie); on an Rgba frame against a grey target
+// alpha becomes 0, as in the reference.
+struct NoTargetSet : std::logic_error { NoTargetSet() : std::logic_error("NoTargetSet") {} };   // fdm.zig:142
+struct NoSourceSet : std::logic_error { NoSourceSet() : std::logic_error("NoSourceSet") {} };   // fdm.zig:143
+template <typename T, template <typename> class Img = Image> class FeatureDistributionMatching {
+    static_assert(PixelTraits<T>::pixel == ZG_PIXEL_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGB_U8 || PixelTraits<T>::pixel == ZG_PIXEL_RGBA_U8,
+                  "FeatureDistributionMatching takes u8, Rgb(u8) and Rgba(u8) (fdm.zig:20)");
+    static constexpr bool on_device = std::is_same<Img<T>, DeviceImage<T>>::value;
+
+  public:
+    FeatureDistributionMatching() = default;
+    FeatureDistributionMatching(const FeatureDistributionMatching &) = delete;
+    FeatureDistributionMatching &operator=(const FeatureDistributionMatching &) = delete;
+    ~FeatureDistributionMatching() { if (records_) zg_free(records_); }
+
+    void setTarget(const Img<T> &target) {                                                // fdm.zig:68-124
+        target_ = target.desc();
+        if constexpr (on_device) {
+            if (!records_) check(zg_malloc(&records_, 512));
+            zg_fdm_moments *m = (zg_fdm_moments *)records_;
+            check(zg_fdm_compute_moments(&target_, m, target.stream()));
+            check(zg_fdm_target_from_moments(m, prepared(), target.stream()));
+        }
+        has_target_ = true;
+    }
+    void setSource(const Img<T> &source) { source_ = &source; }                            // fdm.zig:127-130
+    void update() {                                                                        // fdm.zig:141-273
+        if (!has_target_) throw NoTargetSet();
+        if (!source_) throw NoSourceSet();
+        const zg_image s = source_->desc();
+        if constexpr (on_device) check(zg_fdm_match_frames(&s, 1, nullptr, prepared(), source_->stream()));
+        else check(zg_fdm_match_host(&s, &target_));
+    }
+    void match(const Img<T> &source, const Img<T> &target) {                               // fdm.zig:133-137
+        setTarget(target);
+        setSource(source);
+        update();
+    }
+    // every frame against the target set before, in one chain (on the first frame's stream)
+    void updateFrames(const std::vector<const Img<T> *> &frames) {
+        if (!has_target_) throw NoTargetSet();
+        if (frames.empty()) return;
+        std::vector<zg_image> d;
+        for (const Img<T> *f : frames) d.push_back(f->desc());
+        if constexpr (on_device) check(zg_fdm_match_frames(d.data(), (uint32_t)d.size(), nullptr, prepared(), frames[0]->stream()));
+        else check(zg_fdm_match_frames_host(d.data(), (uint32_t)d.size(), &target_));
+    }
+
+  private:
+    zg_fdm_target *prepared() const { return (zg_fdm_target *)((char *)records_ + 256); }
+    zg_image target_{};
+    const Img<T> *source_ = nullptr;
+    void *records_ = nullptr; // device: the target's moments, and at 256 bytes its zg_fdm_target
+    bool has_target_ = false;
+};
+
 } // namespace zignal
