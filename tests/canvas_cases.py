@@ -143,3 +143,74 @@ def random_commands(n, rows, cols, seed=RANDOM_SEED):
             pts = [(float(np.float32(x + r * np.cos(a))), float(np.float32(y + r * np.sin(a)))) for a, r in zip(ang, rad)]
             out.append(polygon(pts, color, width, mode) if kind == ref.KIND_POLYGON else fill_polygon(pts, color, mode))
     return out
+
+
+# ---- what the GPU tests of the drawing entry points share (shapes, arcs, text) ---------------------------------------------------------
+def same_bytes(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def on_device(host, cmds, draw):
+    """A device copy of `host` after draw(frame, dcmds), dcmds being the packed `cmds` as bytes on the device (an empty list: one zeroed
+    struct, so that there is an address); returns the frame."""
+    import torch
+
+    dev = torch.from_numpy(host.copy()).cuda()
+    dcmds = torch.from_numpy(cmds.view(np.uint8).copy()).cuda() if len(cmds) else torch.zeros(cmds.dtype.itemsize, dtype=torch.uint8, device="cuda")
+    draw(dev, dcmds)
+    return dev.cpu().numpy()
+
+
+def on_host(host, draw_host, *packed):
+    out = host.copy()
+    draw_host(out, *packed)
+    return out
+
+
+def differs(got, want, what, form):
+    bad = np.argwhere((got != want).reshape(got.shape[0], got.shape[1], -1).any(axis=2))
+    return AssertionError(f"{what} ({form}): {len(bad)} pixels differ, first (row, col) {tuple(bad[0])}: got {got[tuple(bad[0])]}, reference {want[tuple(bad[0])]}")
+
+
+def check(want, what, *forms):
+    """Every form — (entry point's name, callable that returns the frame it drew) — equals the restatement's `want`."""
+    for form, draw in forms:
+        got = draw()
+        if not same_bytes(got, want):
+            raise differs(got, want, what, form)
+    return want
+
+
+def replay_captured(frame, draw, load, rounds):
+    """Captures draw() on a side stream, then replays the graph once per (k, how_many) of `rounds`, after load(k, how_many) has
+    refilled the buffers the capture saw and returned what `frame` must hold afterwards."""
+    import torch
+
+    import zignal_amd as zg
+
+    side = torch.cuda.Stream()
+    load(*rounds[0])
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        draw()
+    for k, how_many in rounds:
+        want = load(k, how_many)
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert same_bytes(frame.cpu().numpy(), want), (k, how_many)
+    del graph
+    torch.cuda.synchronize()
+    assert zg.lib().zg_release_graph_scratch() == 0
+
+
+def graph_replay_in_a_fresh_process(module):
+    """tests.<module>.graph_replay() in a process of its own, so that its capture holds the first drawing call the process makes."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", f"from tests.{module} import graph_replay; graph_replay(); print('ok')"], capture_output=True,
+                         text=True, timeout=300, cwd=root)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-3000:]

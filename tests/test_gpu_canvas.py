@@ -8,6 +8,7 @@ import pytest
 import zignal_amd as zg
 from tests import canvas_cases as K
 from tests import canvas_ref as R
+from tests.canvas_cases import same_bytes
 from zignal_amd import canvas
 
 try:
@@ -38,10 +39,6 @@ def on_device(host, commands, count=None, n=None):
     dverts = torch.from_numpy(vertices).cuda() if len(vertices) else None
     canvas.draw(dev, dcmds, count=count, vertices=dverts, n=len(cmds) if n is None else n)
     return dev.cpu().numpy()
-
-
-def same_bytes(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def check(host, commands, what):
@@ -164,6 +161,32 @@ def test_a_thousand_random_commands_with_heavy_overlap(pixel):
     rows, cols = 2 * T + 9, 3 * T + 2
     commands = K.random_commands(1100, rows, cols, K.RANDOM_SEED)  # more than the 1024 commands a workgroup lists between two barriers
     check(background(rows, cols, pixel, 4), commands, pixel)
+
+
+SEAMS = (63, 255, 767, 1023)  # the last entry of a wave, of the first and the third slice of 256, and of a chunk of 1024; its successor follows
+
+
+@pytest.mark.gpu
+def test_order_sensitive_pairs_on_the_wave_slice_and_chunk_seams_of_the_gather():
+    """Where the tile's list is put together from the ballots of four waves, four slices and the chunks, a pair of overlapping
+    translucent rectangles lies with one command on either side of the seam; every other command lies off the frame, has an empty
+    box and must not hit. 17 x 17: two tiles each way, three of them partial, and each pair covers pixels of both tile columns."""
+    host = background(T + 1, T + 1, "rgba_u8", 14)
+    commands = [K.fill_rect(-40.0 - i % 7, -30.0, -35.0, -20.0 - i % 5, (i % 256, 90, 200, 128), SOFT) for i in range(1030)]
+    for k, at in enumerate(SEAMS):  # pair k on rows 4 k .. 4 k + 4: the last one reaches the second tile row
+        commands[at] = K.fill_rect(11.0, 4.0 * k, 17.0, 4.0 * k + 4, (250, 10 + 60 * k, 10, 128), SOFT)
+        commands[at + 1] = K.fill_rect(13.0, 4.0 * k + 1, 17.0, 4.0 * k + 5, (10, 10 + 60 * k, 250, 128), SOFT)
+    want = R.run(host, commands)
+    assert (want != host).any(axis=2)[:, :T].any() and (want != host).any(axis=2)[:, T:].any()
+    for at in SEAMS:
+        swapped = list(commands)
+        swapped[at], swapped[at + 1] = commands[at + 1], commands[at]
+        assert not same_bytes(want, R.run(host, swapped)), at
+    cmds, _ = canvas.pack_commands(commands)
+    for arcs in (False, True):
+        got = K.on_device(host, cmds, lambda dev, dcmds: canvas.draw(dev, dcmds, arcs=arcs))
+        if not same_bytes(got, want):
+            raise K.differs(got, want, "1030 commands, pairs on the seams", "zg_canvas_draw_arcs" if arcs else "zg_canvas_draw")
 
 
 # ---- views ------------------------------------------------------------------------------------------------------------------------------

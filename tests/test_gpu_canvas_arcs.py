@@ -6,9 +6,6 @@ axes, wrapped, negative, above 2 pi, either side of pi, empty and full; order ag
 word, a view, the contract, the old entry point, a captured graph and the Canvas class."""
 import hashlib
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -43,36 +40,19 @@ def make(route, center, radius, a0, a1, color):
 def on_device(host, commands, count=None, n=None, arcs=True):
     """zg_canvas_draw_arcs (arcs=False: zg_canvas_draw) of `commands` into a device copy of `host`; returns the frame."""
     cmds, vertices = canvas.pack_commands(commands)
-    dev = torch.from_numpy(host.copy()).cuda()
-    dcmds = torch.from_numpy(cmds.view(np.uint8).copy()).cuda() if len(cmds) else torch.zeros(40, dtype=torch.uint8, device="cuda")
     dverts = torch.from_numpy(vertices).cuda() if len(vertices) else None
-    canvas.draw(dev, dcmds, count=count, vertices=dverts, n=len(cmds) if n is None else n, arcs=arcs)
-    return dev.cpu().numpy()
+    return K.on_device(host, cmds, lambda dev, dcmds: canvas.draw(dev, dcmds, count=count, vertices=dverts, n=len(cmds) if n is None else n, arcs=arcs))
 
 
 def on_host(host, commands):
-    out = host.copy()
-    canvas.draw_host(out, *canvas.pack_commands(commands))
-    return out
-
-
-def differs(got, want, what, form):
-    bad = np.argwhere((got != want).reshape(got.shape[0], got.shape[1], -1).any(axis=2))
-    return AssertionError(f"{what} ({form}): {len(bad)} pixels differ, first (row, col) {tuple(bad[0])}: got {got[tuple(bad[0])]}, reference {want[tuple(bad[0])]}")
+    return K.on_host(host, canvas.draw_host, *canvas.pack_commands(commands))
 
 
 def check(host, commands, what, host_form=False):
     """The device form (and, asked for, the host form) equals the restatement. Both fail on a library without arcs: there the device
     skips them and the host form refuses them."""
-    want = AR.run(host, commands)
-    got = on_device(host, commands)
-    if not same_bytes(got, want):
-        raise differs(got, want, what, "zg_canvas_draw_arcs")
-    if host_form:
-        got = on_host(host, commands)
-        if not same_bytes(got, want):
-            raise differs(got, want, what, "zg_canvas_draw_host")
-    return want
+    forms = [("zg_canvas_draw_arcs", lambda: on_device(host, commands))] + [("zg_canvas_draw_host", lambda: on_host(host, commands))] * host_form
+    return K.check(AR.run(host, commands), what, *forms)
 
 
 # ---- the reference's own renderings ---------------------------------------------------------------------------------------------------
@@ -333,26 +313,9 @@ def graph_replay():
         count.fill_(how_many)
         return AR.run(host, lists[k][:how_many])
 
-    side = torch.cuda.Stream()
-    load(0, n)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        canvas.draw(frame, dcmds, count=count, vertices=dverts, arcs=True)
-    for k, how_many in ((0, n), (1, n), (2, 7)):
-        want = load(k, how_many)
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert same_bytes(frame.cpu().numpy(), want), (k, how_many)
-    del graph
-    torch.cuda.synchronize()
-    assert zg.lib().zg_release_graph_scratch() == 0
+    K.replay_captured(frame, lambda: canvas.draw(frame, dcmds, count=count, vertices=dverts, arcs=True), load, ((0, n), (1, n), (2, 7)))
 
 
 @pytest.mark.gpu
 def test_draw_arcs_is_captured_as_a_fresh_process_first_canvas_call_and_replays_on_changed_lists():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", "from tests.test_gpu_canvas_arcs import graph_replay; graph_replay(); print('ok')"], capture_output=True,
-                         text=True, timeout=300, cwd=root)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-3000:]
+    K.graph_replay_in_a_fresh_process("test_gpu_canvas_arcs")

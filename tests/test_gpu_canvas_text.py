@@ -4,9 +4,6 @@ one and two bytes a row and a glyph table with offsets, zero advances and a glyp
 each edge and outside; newlines, missing codepoints, empty texts; order and multiplicity on Rgba(u8); the chunk boundary, the count word,
 the contract, a view, a captured graph and the Canvas class."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -48,34 +45,17 @@ def string_of(name):
 def on_device(host, name, commands, count=None, n=None, font=None):
     """zg_canvas_draw_text of `commands` (TR.text dicts) into a device copy of `host`; returns the frame."""
     cmds, cps = ZT.pack_text(commands)
-    dev = torch.from_numpy(host.copy()).cuda()
-    dcmds = torch.from_numpy(cmds.view(np.uint8).copy()).cuda() if len(cmds) else torch.zeros(28, dtype=torch.uint8, device="cuda")
     dcps = torch.from_numpy(cps.view(np.int32).copy()).cuda()
-    ZT.draw_text(dev, font or dfont(name), dcmds, dcps, count=count, n=len(cmds) if n is None else n)
-    return dev.cpu().numpy()
+    return K.on_device(host, cmds, lambda dev, dcmds: ZT.draw_text(dev, font or dfont(name), dcmds, dcps, count=count, n=len(cmds) if n is None else n))
 
 
 def on_host(host, name, commands):
-    out = host.copy()
-    ZT.draw_text_host(out, dfont(name), *ZT.pack_text(commands))
-    return out
-
-
-def differs(got, want, what, form):
-    bad = np.argwhere((got != want).reshape(got.shape[0], got.shape[1], -1).any(axis=2))
-    return AssertionError(f"{what} ({form}): {len(bad)} pixels differ, first (row, col) {tuple(bad[0])}: got {got[tuple(bad[0])]}, reference {want[tuple(bad[0])]}")
+    return K.on_host(host, ZT.draw_text_host, dfont(name), *ZT.pack_text(commands))
 
 
 def check(host, name, commands, what, host_form=False):
-    want = TR.run(host, REF_FONTS[name], commands)
-    got = on_device(host, name, commands)
-    if not same_bytes(got, want):
-        raise differs(got, want, what, "zg_canvas_draw_text")
-    if host_form:
-        got = on_host(host, name, commands)
-        if not same_bytes(got, want):
-            raise differs(got, want, what, "zg_canvas_draw_text_host")
-    return want
+    forms = [("zg_canvas_draw_text", lambda: on_device(host, name, commands))] + [("zg_canvas_draw_text_host", lambda: on_host(host, name, commands))] * host_form
+    return K.check(TR.run(host, REF_FONTS[name], commands), what, *forms)
 
 
 # ---- the three paths ------------------------------------------------------------------------------------------------------------------------
@@ -177,6 +157,24 @@ def test_a_list_longer_than_one_compaction_chunk():
         commands.append(TR.text("I#O", (5.0 + 7 * i, 20.0 + i), (9, 200, 30, 128), 1.0, FAST))
     want = check(host, "8x8", commands, "1046 glyphs")
     assert not same_bytes(want, TR.run(host, REF_FONTS["8x8"], commands[:93] + commands[94:]))
+
+
+@pytest.mark.gpu
+def test_order_sensitive_glyphs_on_the_wave_slice_and_chunk_seams_of_the_gather():
+    """One codepoint a command, so that a glyph's place in the entry list is its command's: pairs of overlapping translucent glyphs lie
+    with one entry on either side of a seam of the gather (between two waves, two slices of 256, two chunks of 1024); every other glyph
+    lies off the frame, has an empty box and must not hit. 17 x 17: two tiles each way, and each pair covers pixels of both tile columns."""
+    host = background(T + 1, T + 1, "rgba_u8", 15)
+    commands = [TR.text("HIO%#&@"[i % 7], (-60.0 - i % 9, -40.0 - i % 4), (i % 256, 90, 200, 128), 1.0, FAST) for i in range(1030)]
+    for k, at in enumerate((63, 255, 767, 1023)):  # pair k from row 3 k on: the last one reaches the second tile row
+        commands[at] = TR.text("#", (9.0, 3.0 * k), (250, 10 + 60 * k, 10, 128), 1.0, FAST)
+        commands[at + 1] = TR.text("%", (10.0, 3.0 * k + 1), (10, 10 + 60 * k, 250, 128), 1.0, FAST)
+    want = check(host, "8x8", commands, "1030 glyphs, pairs on the seams")
+    assert (want != host).any(axis=2)[:, :T].any() and (want != host).any(axis=2)[:, T:].any()
+    for at in (63, 255, 767, 1023):
+        swapped = list(commands)
+        swapped[at], swapped[at + 1] = commands[at + 1], commands[at]
+        assert not same_bytes(want, TR.run(host, REF_FONTS["8x8"], swapped)), at
 
 
 # ---- the device call ------------------------------------------------------------------------------------------------------------------------
@@ -285,7 +283,7 @@ def test_flush_issues_runs_of_text_and_of_everything_else_in_list_order():
         assert cv.commands == []
         got = zg.Image(image).to_numpy()
         if not same_bytes(got, want):
-            raise differs(got, want, "rectangle, text, line, text, text", type(image).__name__)
+            raise K.differs(got, want, "rectangle, text, line, text, text", type(image).__name__)
     # a list order that matters: the line over the first text, under the second
     assert not same_bytes(want, TR.run(CR.run(host, [K.fill_rect(4.0, 3.0, 44.0, 30.0, (20, 30, 200, 160), SOFT), K.line(2.0, 8.0, 50.0, 24.0, (250, 250, 10, 128), 3, SOFT)]),
                                        REF_FONTS["8x8"], [TR.text("HI O", (6.5, 5.0), TRANSLUCENT, 2.0, SOFT), TR.text("OH", (8.0, 14.5), (250, 20, 20, 128), 1.5, FAST)]))
@@ -339,26 +337,9 @@ def graph_replay():
         count.fill_(how_many)
         return TR.run(host, REF_FONTS["8x8"], lists[k][:how_many])
 
-    side = torch.cuda.Stream()
-    load(0, n)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        ZT.draw_text(frame, font, dcmds, dcps, count=count)
-    for k, how_many in ((0, n), (1, n), (2, 5)):
-        want = load(k, how_many)
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert same_bytes(frame.cpu().numpy(), want), (k, how_many)
-    del graph
-    torch.cuda.synchronize()
-    assert zg.lib().zg_release_graph_scratch() == 0
+    K.replay_captured(frame, lambda: ZT.draw_text(frame, font, dcmds, dcps, count=count), load, ((0, n), (1, n), (2, 5)))
 
 
 @pytest.mark.gpu
 def test_draw_text_is_captured_as_a_fresh_process_first_drawing_call_and_replays_on_changed_lists():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", "from tests.test_gpu_canvas_text import graph_replay; graph_replay(); print('ok')"], capture_output=True,
-                         text=True, timeout=300, cwd=root)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-3000:]
+    K.graph_replay_in_a_fresh_process("test_gpu_canvas_text")

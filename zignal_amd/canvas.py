@@ -86,6 +86,29 @@ def has_arcs(commands) -> bool:
     return any(int(c["kind"]) in (L.DRAW_ARC, L.DRAW_FILL_ARC) for c in commands)
 
 
+def _device_lists(who, img, cmds, itemsize, n, count, *lists) -> int:
+    """The checks draw and draw_text (`who`) share: a device image and device tensors (`count` may be None), `cmds` of at least n structs
+    of `itemsize` bytes, `count` of a word. Returns n, by default all that `cmds` holds."""
+    if not img.on_device or not all(_is_torch(t) for t in (cmds, *lists) + (() if count is None else (count,))):
+        raise ValueError(f"{who} takes a device image and device tensors")
+    cap = _bytes_of(cmds) // itemsize
+    n = cap if n is None else int(n)
+    if n > cap or (count is not None and _bytes_of(count) < 4):
+        raise ValueError("cmds or count tensor too small")
+    return n
+
+
+def _run_uploaded(device, stream, call, *arrays):
+    """A flush's device half: uploads the numpy arrays (None stays None; one synchronous copy each), makes `call` with the tensors on
+    `stream` (None: the current one) and records them on it, so that their memory is not reused before the call has run."""
+    tensors = [None if a is None else torch.from_numpy(a).to(device) for a in arrays]
+    with torch.cuda.stream(stream):  # None: no change of stream, and nothing to record
+        call(*tensors)
+    for t in tensors if stream is not None else ():
+        if t is not None:
+            t.record_stream(stream)
+
+
 def draw(image, cmds, count=None, vertices=None, n=None, arcs=False) -> None:
     """zg_canvas_draw, the device-list form: `cmds` is a device tensor holding zg_draw_cmd structs (n of them; by default as many as it
     holds), `count` an optional device tensor whose first 4 bytes are the number of commands to execute (at most n), `vertices` a
@@ -93,12 +116,7 @@ def draw(image, cmds, count=None, vertices=None, n=None, arcs=False) -> None:
     arcs=True: zg_canvas_draw_arcs, the entry point that also draws DRAW_ARC and DRAW_FILL_ARC (zg_canvas_draw skips them); the host
     cannot see a device list, so the caller who built it says whether it may hold arcs."""
     img = image if isinstance(image, Image) else Image(image)
-    if not img.on_device or not _is_torch(cmds) or (count is not None and not _is_torch(count)) or (vertices is not None and not _is_torch(vertices)):
-        raise ValueError("draw takes a device image and device tensors")
-    cap = _bytes_of(cmds) // DRAW_CMD_DTYPE.itemsize
-    n = cap if n is None else int(n)
-    if n > cap or (count is not None and _bytes_of(count) < 4):
-        raise ValueError("cmds or count tensor too small")
+    n = _device_lists("draw", img, cmds, DRAW_CMD_DTYPE.itemsize, n, count, *(() if vertices is None else (vertices,)))
     if vertices is not None and (vertices.dtype != torch.float32 or not vertices.is_contiguous()):
         raise ValueError("vertices must be a contiguous float32 tensor of (x, y) pairs")
     nv = 0 if vertices is None else vertices.numel() // 2
@@ -244,36 +262,17 @@ class Canvas:
         if not self.image.on_device:
             T.draw_text_host(self.image, font, cmds, cps)
             return
-        if not len(cps):
-            return
-        dev = self.image.data.device
-        dcmds = torch.from_numpy(cmds.view(np.uint8)).to(dev)
-        dcps = torch.from_numpy(cps.view(np.int32)).to(dev)
-        if stream is None:
-            T.draw_text(self.image, font, dcmds, dcps)
-        else:
-            with torch.cuda.stream(stream):
-                T.draw_text(self.image, font, dcmds, dcps)
-            dcmds.record_stream(stream)
-            dcps.record_stream(stream)
+        if len(cps):
+            _run_uploaded(self.image.data.device, stream, lambda dcmds, dcps: T.draw_text(self.image, font, dcmds, dcps), cmds.view(np.uint8), cps.view(np.int32))
 
     def _flush_shapes(self, commands, stream) -> None:
         cmds, vertices = pack_commands(commands)
         if not self.image.on_device:
             draw_host(self.image, cmds, vertices)
             return
-        dev = self.image.data.device
-        dcmds = torch.from_numpy(cmds.view(np.uint8)).to(dev)
-        dverts = torch.from_numpy(vertices).to(dev) if len(vertices) else None
         arcs = has_arcs(cmds)
-        if stream is None:
-            draw(self.image, dcmds, vertices=dverts, arcs=arcs)
-        else:
-            with torch.cuda.stream(stream):
-                draw(self.image, dcmds, vertices=dverts, arcs=arcs)
-            dcmds.record_stream(stream)
-            if dverts is not None:
-                dverts.record_stream(stream)
+        _run_uploaded(self.image.data.device, stream, lambda dcmds, dverts: draw(self.image, dcmds, vertices=dverts, arcs=arcs), cmds.view(np.uint8),
+                      vertices if len(vertices) else None)
 
     def draw(self, cmds_tensor, count=None, vertices=None, arcs=False) -> None:
         """The device-list form: see zignal_amd.canvas.draw."""

@@ -9,14 +9,13 @@
 //                             fillArcFast's spans, fillArcSoft's coverage) — in k_canvas<PIX, true> only, behind zg_canvas_draw_arcs
 // composited with Rgba.blend(.normal) and convertColor exactly as Image.insert does (zg_blend.h).
 //
-// The reference's result at a pixel is a fold, in call order, over every write any call makes to that pixel, and blending writes do not
-// commute. So the device gathers: one workgroup per 16 x 16 pixel tile, one lane per pixel. The lane keeps its pixel in registers, walks the
-// command list in order, applies each write that reaches its pixel — as often as the reference makes it — and stores once if anything did.
+// The device gathers (zg_canvas_tile.h: one workgroup per 16 x 16 pixel tile, one lane per pixel, the pixel in registers, the list's commands
+// that reach the tile handed to the lanes in list order): each lane applies every write that reaches its pixel, as often as the reference makes it.
 //   k_canvas_prep   one lane per command: checks the command against the contract and writes the pixel box that bounds everything the command
 //                   can write (empty for a command that is skipped, draws nothing or lies past the count word)
-//   k_canvas        (<PIX, false>: every kind but the arcs, zg_canvas_draw; <PIX, true>: the arcs too, zg_canvas_draw_arcs — the routines are shared,
-//                   what knows an arc is compiled into the second only, so the first is the kernel it was before there were arcs) per tile: 1024 commands at a time, each lane tests four commands' boxes against the tile and the hits are compacted in list
-//                   order (ballot + prefix, no atomics: the order is the list's by construction); then every lane applies the tile's commands.
+//   k_canvas        (<PIX, false>: every kind but the arcs, zg_canvas_draw; <PIX, true>: the arcs too, zg_canvas_draw_arcs — the routines are
+//                   shared, what knows an arc is compiled into the second only) per tile: tile_gather with a command's box and, for lines and
+//                   circles, its shape as the test, and Cv::apply as what a hit does.
 //                   A command is expanded into the reference's sequence of internal calls on the fly (a rectangle outline is four lines, a thick
 //                   fast line a polygon and two discs ...), so no expanded list and no per-tile list ever exists in memory: the only scratch is the
 //                   8 bytes per command of the boxes, a size the host knows without reading the (device-resident) commands.
@@ -26,8 +25,7 @@
 // only be sized for the worst case, n x 64 edges x 32768 steps): the integer Bresenham line has a closed form (tests/canvas_ref.py holds it to
 // the literal walk); fillCircleFast's `y += 1` in f32 is replayed a binade at a time (exact inside one); Wu's `intery += gradient` and the
 // Bresenham circle are re-walked by each lane up to its own step, after a tile-level test has let through only the tiles near the line or ring.
-#include "zg_internal.h"
-#include "zg_blend.h"
+#include "zg_canvas_tile.h"
 // every routine of the canvas kernels is inlined (no calls, so no stack): here the device maths too, which elsewhere is left to the compiler
 #pragma clang attribute push(__attribute__((always_inline)), apply_to = function)
 #include "zg_devmath.h"
@@ -40,12 +38,9 @@
 
 namespace zg {
 
-constexpr int CV_TILE = 16;
-constexpr int CV_CHUNK = 1024; // commands a workgroup tests against its tile between two barriers
 constexpr int CV_POINTS = ZG_CANVAS_MAX_CURVE_POINTS; // vertices of the largest polygon poly_fill is handed
 constexpr int CV_CURVE_BASE = 8; // a Bézier's points sit in s_vx / s_vy from here: below it a thick fast line keeps its four corners
 constexpr float CV_TILE_REACH = 11.4f; // from a tile's centre (7.5, 7.5) to its farthest pixel centre, rounded up
-using Rgba8 = typename Px<ZG_PIXEL_RGBA_U8>::Vec;
 
 // The reference's tessellation constants (:36-48): segment counts are max(min, min(max, trunc(estimated length / pixels per segment)))
 constexpr int CV_BEZIER_MAX_SEGMENTS = 200, CV_SPLINE_MAX_SEGMENTS = 50, CV_SPLINE_MIN_SEGMENTS = 4, CV_QUADRATIC_MIN_SEGMENTS = 3;
@@ -307,41 +302,20 @@ template <bool ARCS> __device__ inline bool cv_tile_may_touch(const zg_draw_cmd 
     return true;
 }
 
-__device__ inline float cv_clamp(float v, float lo, float hi) { return fmaxf(lo, fminf(v, hi)); } // std.math.clamp
-__device__ inline Rgba8 cv_fade(Rgba8 c, float alpha) { // Rgba(u8).fade (color.zig:447-456)
-    c[3] = (uint8_t)(int)truncf((float)c[3] * cv_clamp(alpha, 0.0f, 1.0f));
-    return c;
-}
 __device__ inline float cv_fpart(float x) { return x - floorf(x); }
 __device__ inline float cv_rfpart(float x) { return 1.0f - cv_fpart(x); }
-template <int PIX> struct Cv {
-    using P = Px<PIX>;
-    typename P::Vec px;
-    bool dirty, inside;
-    int col, row, tx0, ty0, tid;
+template <int PIX> struct Cv : TilePixel<PIX> {
+    using TilePixel<PIX>::col;
+    using TilePixel<PIX>::row;
+    using TilePixel<PIX>::solid;
+    using TilePixel<PIX>::pixel;
+    int tx0, ty0, tid;
     float fx, fy, fcols, frows;
     float *s_vx, *s_vy, *s_ix; // polygon vertices [CV_POINTS], [CV_POINTS]; sorted intersections [16][CV_POINTS]
     float *s_row;              // what a disc or an axis-aligned line computes once per tile row or column [16][3]
     int *s_icnt;               // intersections per tile row [16]
     unsigned long long *s_near; // a curve's segments that can reach the tile, one bit each [4]
 
-    __device__ __forceinline__ void solid(Rgba8 c) { // dest.* = convertColor(T, color)
-        if (!inside) return;
-        px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
-        dirty = true;
-    }
-    // setPixel with an Rgba colour (:504-514): it hands assignPixel (image.zig:67-94) convertColor(T, color), so only an Rgba destination still
-    // has an Rgba sample to blend (when a != 255). On u8 and Rgb the converted sample has lost its alpha and is stored whatever the alpha was,
-    // a faded alpha of 0 included.
-    __device__ __forceinline__ void pixel(Rgba8 c) {
-        if (!inside) return;
-        if constexpr (PIX == ZG_PIXEL_RGBA_U8) {
-            if (c[3] != 255) blend_u8(px, c, 1); else px = c;
-        } else {
-            px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
-        }
-        dirty = true;
-    }
     __device__ __forceinline__ void point(float x, float y, Rgba8 c) { // setPoint (:518-523)
         if (floorf(x) == fx && floorf(y) == fy) pixel(c);
     }
@@ -353,8 +327,8 @@ template <int PIX> struct Cv {
     }
     // clampRectToImage (:62-79)
     __device__ __forceinline__ bool clamp_rect(float l, float t, float r, float b, int &left, int &top, int &right, int &bottom) const {
-        left = (int)cv_clamp(l, 0.0f, fcols); top = (int)cv_clamp(t, 0.0f, frows);
-        right = (int)cv_clamp(r, 0.0f, fcols); bottom = (int)cv_clamp(b, 0.0f, frows);
+        left = (int)clampf(l, 0.0f, fcols); top = (int)clampf(t, 0.0f, frows);
+        right = (int)clampf(r, 0.0f, fcols); bottom = (int)clampf(b, 0.0f, frows);
         return !(left >= right || top >= bottom);
     }
     __device__ __forceinline__ float tile_distance(float cx, float cy) const { // from the tile's centre to (cx, cy)
@@ -377,8 +351,8 @@ template <int PIX> struct Cv {
     template <bool ARC> __device__ __forceinline__ void ring_t(float cx, float cy, float inner, float outer, Rgba8 color, int mode, const CvArc &arc) {
         const float dc = tile_distance(cx, cy);
         if (dc - CV_TILE_REACH > outer + 3.0f || (inner > 0 && dc + CV_TILE_REACH < inner - 3.0f)) return; // the tile misses the ring
-        const int left = (int)roundf(cv_clamp(cx - outer - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - outer - 1, 0.0f, frows));
-        const int right = (int)roundf(cv_clamp(cx + outer + 1, 0.0f, fcols)), bottom = (int)roundf(cv_clamp(cy + outer + 1, 0.0f, frows));
+        const int left = (int)roundf(clampf(cx - outer - 1, 0.0f, fcols)), top = (int)roundf(clampf(cy - outer - 1, 0.0f, frows));
+        const int right = (int)roundf(clampf(cx + outer + 1, 0.0f, fcols)), bottom = (int)roundf(clampf(cy + outer + 1, 0.0f, frows));
         if (left >= right || top >= bottom) return;
         if (col < left || col >= right || row < top || row >= bottom) return;
         const float y = fy - cy, x = fx - cx;
@@ -390,10 +364,10 @@ template <int PIX> struct Cv {
             float alpha = 1.0f;
             if (dist > outer - 0.5f) alpha = fminf(alpha, outer + 0.5f - dist);
             if (inner > 0 && dist < inner + 0.5f) alpha = fminf(alpha, dist - (inner - 0.5f));
-            const float coverage = cv_clamp(alpha, 0.0f, 1.0f);
+            const float coverage = clampf(alpha, 0.0f, 1.0f);
             if (coverage <= 0) return;
             if constexpr (ARC) { if (!arc.full && !cv_arc_contains(arc, dev_atan2f(y, x))) return; }
-            pixel(cv_fade(color, coverage));
+            pixel(fade(color, coverage));
         } else {
             const bool inside_outer = dist_sq <= outer * outer;
             const bool outside_inner = inner <= 0 || dist_sq >= inner * inner;
@@ -530,8 +504,8 @@ template <int PIX> struct Cv {
     // fillArcSoft (:1179-1218) with calculateArcCoverage (:1149-1176)
     __device__ __forceinline__ void arc_fill_soft(float cx, float cy, float radius, Rgba8 color, const CvArc &arc) {
         if (tile_distance(cx, cy) - CV_TILE_REACH > radius + 3.0f) return;
-        const int left = (int)roundf(cv_clamp(cx - radius - 1, 0.0f, fcols)), top = (int)roundf(cv_clamp(cy - radius - 1, 0.0f, frows));
-        const int right = (int)roundf(cv_clamp(cx + radius + 1, 0.0f, fcols)), bottom = (int)roundf(cv_clamp(cy + radius + 1, 0.0f, frows));
+        const int left = (int)roundf(clampf(cx - radius - 1, 0.0f, fcols)), top = (int)roundf(clampf(cy - radius - 1, 0.0f, frows));
+        const int right = (int)roundf(clampf(cx + radius + 1, 0.0f, fcols)), bottom = (int)roundf(clampf(cy + radius + 1, 0.0f, frows));
         if (left >= right || top >= bottom) return;
         if (col < left || col >= right || row < top || row >= bottom) return;
         const float y = fy - cy, x = fx - cx;
@@ -545,7 +519,7 @@ template <int PIX> struct Cv {
         const bool near_start = start_cross < 1.0f && start_cross_product < eps, near_end = end_cross < 1.0f && end_cross_product > -eps;
         if (!in_arc && !near_start && !near_end) return;
         const float dist = sqrtf(dist_sq);
-        const float circ_coverage = dist <= radius - 1.0f ? 1.0f : (dist < radius + 1.0f ? cv_clamp(radius - dist + 0.5f, 0.0f, 1.0f) : 0.0f);
+        const float circ_coverage = dist <= radius - 1.0f ? 1.0f : (dist < radius + 1.0f ? clampf(radius - dist + 0.5f, 0.0f, 1.0f) : 0.0f);
         float coverage;
         if (!in_arc) {
             float edge_coverage = 0.0f;
@@ -557,7 +531,7 @@ template <int PIX> struct Cv {
             if (start_cross < 1.0f && start_cross_product >= -eps) coverage = fminf(coverage, start_cross);
             if (end_cross < 1.0f && end_cross_product <= eps) coverage = fminf(coverage, end_cross);
         }
-        if (coverage > 0) pixel(cv_fade(color, coverage));
+        if (coverage > 0) pixel(fade(color, coverage));
     }
 
     // fillPolygon (:935-1017) of the n >= 3 vertices in s_vx / s_vy. Lanes 0-15 each take one row of the tile: the intersections in the
@@ -596,8 +570,8 @@ template <int PIX> struct Cv {
                     float alpha = 1.0f;
                     if (x < left_edge + 1) alpha = fminf(alpha, x + 0.5f - left_edge);
                     if (x > right_edge - 1) alpha = fminf(alpha, right_edge - (x - 0.5f));
-                    alpha = cv_clamp(alpha, 0.0f, 1.0f);
-                    if (alpha > 0) pixel(cv_fade(color, alpha));
+                    alpha = clampf(alpha, 0.0f, 1.0f);
+                    if (alpha > 0) pixel(fade(color, alpha));
                 }
             } else {
                 span(left_edge, right_edge, fy, color);
@@ -636,10 +610,10 @@ template <int PIX> struct Cv {
         if (fabsf(y2 - y1) < 0.01f) {
             const float y = roundf(y1), min_x = fminf(x1, x2), max_x = fmaxf(x1, x2);
             const float left_x = floorf(min_x), right_x = ceilf(max_x);
-            if (min_x > left_x) point(left_x, y, cv_fade(c2, min_x - left_x));
+            if (min_x > left_x) point(left_x, y, fade(c2, min_x - left_x));
             const float solid_start = ceilf(min_x), solid_end = floorf(max_x);
             if (solid_end >= solid_start) span(solid_start, solid_end, y, c2);
-            if (max_x < right_x) point(right_x, y, cv_fade(c2, right_x - max_x));
+            if (max_x < right_x) point(right_x, y, fade(c2, right_x - max_x));
             return;
         }
         const bool steep = fabsf(y2 - y1) > fabsf(x2 - x1);
@@ -651,22 +625,22 @@ template <int PIX> struct Cv {
         float x_px1, x_px2, intery;
         {
             const float x_end = roundf(x1), y_end = y1 + gradient * (x_end - x1), x_gap = cv_rfpart(x1 + 0.5f), y_px = floorf(y_end);
-            if (steep) { point(y_px, x_end, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
-            else { point(x_end, y_px, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            if (steep) { point(y_px, x_end, fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, fade(c2, cv_fpart(y_end) * x_gap)); }
+            else { point(x_end, y_px, fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, fade(c2, cv_fpart(y_end) * x_gap)); }
             x_px1 = x_end;
             intery = y_end + gradient;
         }
         {
             const float x_end = roundf(x2), y_end = y2 + gradient * (x_end - x2), x_gap = cv_fpart(x2 + 0.5f), y_px = floorf(y_end);
-            if (steep) { point(y_px, x_end, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
-            else { point(x_end, y_px, cv_fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, cv_fade(c2, cv_fpart(y_end) * x_gap)); }
+            if (steep) { point(y_px, x_end, fade(c2, cv_rfpart(y_end) * x_gap)); point(y_px + 1, x_end, fade(c2, cv_fpart(y_end) * x_gap)); }
+            else { point(x_end, y_px, fade(c2, cv_rfpart(y_end) * x_gap)); point(x_end, y_px + 1, fade(c2, cv_fpart(y_end) * x_gap)); }
             x_px2 = x_end;
         }
         if (!(major > x_px1 && major < x_px2)) return;
         const int steps = (int)(major - x_px1) - 1; // additions before the loop reaches this column
         for (int k = 0; k < steps; ++k) intery += gradient;
-        if (steep) { point(intery, major, cv_fade(c2, cv_rfpart(intery))); point(floorf(intery) + 1, major, cv_fade(c2, cv_fpart(intery))); }
-        else { point(major, intery, cv_fade(c2, cv_rfpart(intery))); point(major, floorf(intery) + 1, cv_fade(c2, cv_fpart(intery))); }
+        if (steep) { point(intery, major, fade(c2, cv_rfpart(intery))); point(floorf(intery) + 1, major, fade(c2, cv_fpart(intery))); }
+        else { point(major, intery, fade(c2, cv_rfpart(intery))); point(major, floorf(intery) + 1, fade(c2, cv_fpart(intery))); }
     }
 
     __device__ __forceinline__ static float perpendicular_alpha(float sample, float center, float half_width) { // :491-496
@@ -719,7 +693,7 @@ template <int PIX> struct Cv {
             if (ok && col >= left && col < right && row >= top && row < bottom) {
                 if (alpha > 0) {
                     if (is_horizontal && alpha >= 1.0f && color[3] == 255) solid(color); // setHorizontalSpan over the box's columns
-                    else pixel(cv_fade(color, alpha));
+                    else pixel(fade(color, alpha));
                 }
             }
             ring(p1x, p1y, 0.0f, half_width, color, ZG_DRAW_SOFT);
@@ -731,13 +705,13 @@ template <int PIX> struct Cv {
                         left, top, right, bottom)) return;
         if (col < left || col >= right || row < top || row >= bottom) return;
         const float dpx = fx - p1x, dpy = fy - p1y;
-        const float t = cv_clamp((dpx * dx + dpy * dy) * inv_length_sq, 0.0f, 1.0f);
+        const float t = clampf((dpx * dx + dpy * dy) * inv_length_sq, 0.0f, 1.0f);
         const float dist_x = dpx - t * dx, dist_y = dpy - t * dy;
         const float dist = sqrtf(dist_x * dist_x + dist_y * dist_y);
         if (dist > half_width + 0.5f) return;
         float alpha = 1.0f;
         if (dist > half_width - 0.5f) alpha = half_width + 0.5f - dist;
-        if (alpha > 0) pixel(cv_fade(color, alpha));
+        if (alpha > 0) pixel(fade(color, alpha));
     }
 
     // evalQuadraticBezier (:1360-1368) and evalCubicBezier (:1373-1383), the sums left to right as written
@@ -881,8 +855,7 @@ template <int PIX> struct Cv {
     // count — is worked out here, once; an arc then takes the circle's, the lines' or the polygon's route below, so that the large routines
     // keep one call site each, or one of the two fills of its own.
     template <bool ARCS> __device__ __forceinline__ void apply(const zg_draw_cmd &c, const float *vertices) {
-        Rgba8 color;
-        color[0] = c.color[0]; color[1] = c.color[1]; color[2] = c.color[2]; color[3] = c.color[3];
+        const Rgba8 color = rgba_of(c.color);
         int kind = c.kind;
         CvArc arc = {};
         arc.full = true;
@@ -938,65 +911,22 @@ template <int PIX> struct Cv {
 
 template <int PIX, bool ARCS>
 __global__ __launch_bounds__(256) void k_canvas(DImg img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, const ushort4 *boxes) {
-    using P = Px<PIX>;
-    __shared__ uint16_t s_list[CV_CHUNK];
-    __shared__ int s_wave_count[CV_CHUNK / 64];
     __shared__ float s_vx[CV_POINTS], s_vy[CV_POINTS], s_ix[CV_TILE * CV_POINTS];
     __shared__ float s_row[CV_TILE * 3];
     __shared__ int s_icnt[CV_TILE];
     __shared__ unsigned long long s_near[4];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     Cv<PIX> cv;
-    cv.tid = tid;
+    cv.place(img);
+    cv.tid = (int)threadIdx.x;
     cv.tx0 = (int)blockIdx.x * CV_TILE; cv.ty0 = (int)blockIdx.y * CV_TILE;
-    cv.col = cv.tx0 + (tid & 15); cv.row = cv.ty0 + (tid >> 4);
     cv.fx = (float)cv.col; cv.fy = (float)cv.row; cv.fcols = (float)img.cols; cv.frows = (float)img.rows;
-    cv.inside = cv.col < img.cols && cv.row < img.rows;
-    cv.dirty = false;
-    cv.px = P::zero();
     cv.s_vx = s_vx; cv.s_vy = s_vy; cv.s_ix = s_ix; cv.s_icnt = s_icnt; cv.s_row = s_row; cv.s_near = s_near;
-    const size_t index = (size_t)cv.row * img.stride + (size_t)cv.col;
-    bool loaded = false;
-    // CV_CHUNK commands at a time, in CV_CHUNK / 256 slices of 256 (slice j: commands base + 256 j + tid): one pair of barriers per chunk
-    for (uint32_t base = 0; base < n; base += CV_CHUNK) {
-        bool hit[CV_CHUNK / 256];
-        unsigned long long ballot[CV_CHUNK / 256];
-#pragma unroll
-        for (int j = 0; j < CV_CHUNK / 256; ++j) {
-            const uint32_t i = base + 256u * j + (uint32_t)tid;
-            hit[j] = false;
-            if (i < n) {
-                const ushort4 b = boxes[i];
-                hit[j] = (int)b.x < cv.tx0 + CV_TILE && (int)b.z > cv.tx0 && (int)b.y < cv.ty0 + CV_TILE && (int)b.w > cv.ty0;
-                if (hit[j]) hit[j] = cv_tile_may_touch<ARCS>(cmds[i], cv.tx0, cv.ty0); // lines and circles: the box is mostly empty
-            }
-            ballot[j] = __ballot(hit[j]);
-            if (lane == 0) s_wave_count[4 * j + wave] = __popcll(ballot[j]);
-        }
-        __syncthreads();
-        int total = 0; // list position = the commands of earlier slices, then of earlier waves of this slice, then of earlier lanes
-#pragma unroll
-        for (int j = 0; j < CV_CHUNK / 256; ++j) {
-            int before = total;
-            for (int w = 0; w < 4; ++w) {
-                const int cnt = s_wave_count[4 * j + w];
-                if (w < wave) before += cnt;
-                total += cnt;
-            }
-            if (hit[j]) s_list[before + __popcll(ballot[j] & ((1ull << lane) - 1ull))] = (uint16_t)(256 * j + tid);
-        }
-        __syncthreads();
-        if (total > 0 && !loaded) {
-            if (cv.inside) cv.px = P::load(img.data, index);
-            loaded = true;
-        }
-        for (int k = 0; k < total; ++k) {
-            const uint32_t ci = base + (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[k]);
-            cv.template apply<ARCS>(cmds[ci], vertices);
-        }
-        __syncthreads();
-    }
-    if (cv.dirty && cv.inside) P::store(img.data, index, cv.px);
+    tile_gather<PIX>(
+        img, cv, n,
+        [&](uint32_t i) { // the box, then for lines and circles, whose boxes are mostly empty, the shape itself
+            return tile_meets_box(boxes[i], cv.tx0, cv.ty0) && cv_tile_may_touch<ARCS>(cmds[i], cv.tx0, cv.ty0);
+        },
+        [&](uint32_t i) { cv.template apply<ARCS>(cmds[i], vertices); });
 }
 
 template <typename T> __global__ __launch_bounds__(256) void k_canvas_build(const T *list, const uint32_t *count, uint32_t capacity, float radius, uint32_t color,
@@ -1019,24 +949,19 @@ template <typename T> __global__ __launch_bounds__(256) void k_canvas_build(cons
     out[i] = c;
 }
 
-static int check_canvas_image(const zg_image *img, bool device_pointer) {
-    if (const int rc = check_image(img, "img", device_pointer)) return rc;
-    ZG_REQUIRE(img->pixel == ZG_PIXEL_U8 || img->pixel == ZG_PIXEL_RGB_U8 || img->pixel == ZG_PIXEL_RGBA_U8, ZG_ERR_UNSUPPORTED,
-               "canvas_draw: pixel type %d (u8, Rgb(u8) and Rgba(u8) are drawn on)", img->pixel);
-    ZG_REQUIRE(img->rows <= ZG_CANVAS_MAX_SIZE && img->cols <= ZG_CANVAS_MAX_SIZE, ZG_ERR_UNSUPPORTED, "canvas_draw: %u x %u image (at most %u each way)",
-               img->rows, img->cols, ZG_CANVAS_MAX_SIZE);
+// What every entry point checks first. who: the entry point, as the null checks' messages name it
+static int check_draw_args(const zg_image *img, bool device_pointer, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, uint32_t n_vertices, const char *who) {
+    if (const int rc = check_draw_image(img, device_pointer, "canvas_draw")) return rc;
+    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "%s: null cmds", who);
+    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "%s: null vertices", who);
     return ZG_OK;
 }
 
-template <int PIX> static void launch_canvas(bool arcs, dim3 grid, hipStream_t s, DImg d, const zg_draw_cmd *cmds, uint32_t n, const float *vertices,
-                                             const ushort4 *boxes) {
-    if (arcs) k_canvas<PIX, true><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
-    else k_canvas<PIX, false><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
-}
-
+// The device lists of entry point `who` drawn into a device image (the host form hands over its staged copies, which pass the checks again).
 // arcs: the kernel that knows drawArc and fillArc; without it they are skipped as no kinds
 static int canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
-                       hipStream_t s, bool arcs) {
+                       hipStream_t s, bool arcs, const char *who) {
+    if (const int rc = check_draw_args(img, true, cmds, n, vertices, n_vertices, who)) return rc;
     ZG_REQUIRE(n <= ZG_CANVAS_MAX_COMMANDS, ZG_ERR_UNSUPPORTED, "canvas_draw: %u commands (at most %u a call)", n, ZG_CANVAS_MAX_COMMANDS);
     if (n == 0 || img->rows == 0 || img->cols == 0) return ZG_OK;
     ScratchBlock sc(s);
@@ -1046,13 +971,13 @@ static int canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n,
     if ((rc = sc.alloc())) return rc;
     k_canvas_prep<<<ceil_div(n, 256), 256, 0, s>>>(cmds, n, count_device, vertices, n_vertices, (int)img->rows, (int)img->cols, boxes, arcs);
     if ((rc = launch_ok("k_canvas_prep"))) return rc;
-    const dim3 grid(ceil_div(img->cols, CV_TILE), ceil_div(img->rows, CV_TILE));
+    const dim3 grid = tile_grid(img);
     const DImg d = dimg(img);
-    switch (img->pixel) {
-    case ZG_PIXEL_U8: launch_canvas<ZG_PIXEL_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
-    case ZG_PIXEL_RGB_U8: launch_canvas<ZG_PIXEL_RGB_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
-    default: launch_canvas<ZG_PIXEL_RGBA_U8>(arcs, grid, s, d, cmds, n, vertices, boxes); break;
-    }
+    dispatch_u8_pixel(img->pixel, [&](auto pix) {
+        constexpr int PIX = decltype(pix)::value;
+        if (arcs) k_canvas<PIX, true><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
+        else k_canvas<PIX, false><<<grid, 256, 0, s>>>(d, cmds, n, vertices, boxes);
+    });
     return launch_ok(arcs ? "k_canvas (arcs)" : "k_canvas");
 }
 
@@ -1074,24 +999,16 @@ uint32_t zg_canvas_tile(void) { return CV_TILE; }
 
 int zg_canvas_draw(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
                    zg_stream stream) {
-    if (const int rc = check_canvas_image(img, true)) return rc;
-    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
-    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
-    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), false);
+    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), false, "canvas_draw");
 }
 
 int zg_canvas_draw_arcs(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const uint32_t *count_device, const float *vertices, uint32_t n_vertices,
                         zg_stream stream) {
-    if (const int rc = check_canvas_image(img, true)) return rc;
-    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_arcs: null cmds");
-    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_arcs: null vertices");
-    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), true);
+    return canvas_draw(img, cmds, n, count_device, vertices, n_vertices, as_stream(stream), true, "canvas_draw_arcs");
 }
 
 int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n, const float *vertices, uint32_t n_vertices) {
-    if (const int rc = check_canvas_image(img, false)) return rc;
-    ZG_REQUIRE(n == 0 || cmds != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null cmds");
-    ZG_REQUIRE(n_vertices == 0 || vertices != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw: null vertices");
+    if (const int rc = check_draw_args(img, false, cmds, n, vertices, n_vertices, "canvas_draw")) return rc;
     bool arcs = false; // the host sees the list: the larger kernel only when it holds an arc
     for (uint32_t i = 0; i < n; ++i) {
         const int bad = cv_check(cmds[i], vertices, n_vertices, true);
@@ -1112,7 +1029,7 @@ int zg_canvas_draw_host(const zg_image *img, const zg_draw_cmd *cmds, uint32_t n
     if ((rc = sc.alloc())) return rc;
     if ((rc = upload_pageable(dcmds, cmds, (size_t)n * sizeof(zg_draw_cmd), nullptr))) return rc;
     if (n_vertices && (rc = upload_pageable(dvertices, vertices, 2 * (size_t)n_vertices * sizeof(float), nullptr))) return rc;
-    return host_in_place(img, true, [&](const zg_image *d) { return canvas_draw(d, dcmds, n, nullptr, dvertices, n_vertices, nullptr, arcs); });
+    return host_in_place(img, true, [&](const zg_image *d) { return canvas_draw(d, dcmds, n, nullptr, dvertices, n_vertices, nullptr, arcs, "canvas_draw"); });
 }
 
 int zg_canvas_cmds_from_hough_lines(const zg_hough_line *lines, const uint32_t *counts, uint32_t capacity, const uint8_t *color, uint32_t width, int mode,

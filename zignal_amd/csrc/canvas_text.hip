@@ -4,17 +4,15 @@
 //   renderGlyphFastScaled  :1586-1605  a block of pixels per lit bit, clipped to the text rectangle; neighbouring blocks overlap at a
 //                                      fractional scale, so one glyph can write a pixel two or four times
 //   renderGlyphSoftScaled  :1609-1658  per destination pixel the box-filtered coverage of the source bits as alpha
-// composited exactly as the canvas composites (zg_blend.h). It gathers as k_canvas does: one workgroup per 16 x 16 tile, one lane per
-// pixel, the pixel kept in registers, every write applied in the reference's order and as often as the reference makes it, one store.
+// composited exactly as the canvas composites (zg_blend.h), through the gather and the pixel writer k_canvas uses (zg_canvas_tile.h): every
+// write is applied in the reference's order and as often as the reference makes it.
 //   k_text_prep   one lane per command: checks the command, runs getTextBounds and then the pen — two sequential f32 recurrences that must
 //                 not re-associate — and writes one entry per codepoint (pen position, resolved glyph, pixel box) and the command's clip
 //                 rectangle. A command's entries begin at the sum of the codepoints of the commands before it, so the entries are in
 //                 (command, codepoint) order by construction and their number is bounded by what the host knows (n_codepoints).
-//   k_text        per tile: 1024 entries at a time, each lane tests four entries' boxes against the tile and the hits are compacted in order
-//                 (ballot + prefix, no atomics); then every lane applies the tile's glyphs.
-// The routines the text needs from the canvas (setPixel's rule, fade) are restated here, not shared: canvas.hip is unchanged.
-#include "zg_internal.h"
-#include "zg_blend.h"
+//   k_text        per tile: tile_gather over the entries, with an entry's box as the test and its glyph, by one of the three paths, as what
+//                 a hit does.
+#include "zg_canvas_tile.h"
 #include "zg_scan.h"
 
 #include <cmath>
@@ -24,10 +22,6 @@
 #pragma clang fp contract(off)
 
 namespace zg {
-
-constexpr int TX_TILE = 16;   // zg_canvas_tile()
-constexpr int TX_CHUNK = 1024; // entries a workgroup tests against its tile between two barriers
-using TxRgba = typename Px<ZG_PIXEL_RGBA_U8>::Vec;
 
 // One codepoint of one command as k_text_prep resolved it. 32 bytes.
 struct TxEntry {
@@ -189,11 +183,6 @@ __global__ __launch_bounds__(256) void k_text_prep(zg_font font, const zg_text_c
     }
 }
 
-__device__ inline float tx_clamp(float v, float lo, float hi) { return fmaxf(lo, fminf(v, hi)); } // std.math.clamp
-__device__ inline TxRgba tx_fade(TxRgba c, float alpha) { // Rgba(u8).fade (color.zig:447-456)
-    c[3] = (uint8_t)(int)truncf((float)c[3] * tx_clamp(alpha, 0.0f, 1.0f));
-    return c;
-}
 // getGlyphBit (:1476-1482): bits LSB first; an index past the glyph's slice reads 0
 __device__ inline bool tx_bit(const uint8_t *char_data, int len, int row, int col, int bytes_per_row) {
     const int at = row * bytes_per_row + (col >> 3);
@@ -201,24 +190,12 @@ __device__ inline bool tx_bit(const uint8_t *char_data, int len, int row, int co
     return (char_data[at] >> (col & 7)) & 1;
 }
 
-template <int PIX> struct Tx {
-    using P = Px<PIX>;
-    typename P::Vec px;
-    bool dirty, inside;
-    int col, row;
+template <int PIX> struct Tx : TilePixel<PIX> {
+    using TilePixel<PIX>::col;
+    using TilePixel<PIX>::row;
+    using TilePixel<PIX>::pixel;
 
-    // setPixel with an Rgba colour (:504-514): only an Rgba destination still has an Rgba sample to blend (when a != 255); on u8 and Rgb the
-    // converted sample is stored whatever the alpha was. renderGlyphUnscaled's hoisted form (:1559-1579) is the same rule.
-    __device__ __forceinline__ void pixel(TxRgba c) {
-        if constexpr (PIX == ZG_PIXEL_RGBA_U8) {
-            if (c[3] != 255) blend_u8(px, c, 1); else px = c;
-        } else {
-            px = convert_px<ZG_PIXEL_RGBA_U8, PIX>(c);
-        }
-        dirty = true;
-    }
-
-    __device__ __forceinline__ void unscaled(const TxEntry &e, const uint8_t *data, TxRgba color) {
+    __device__ __forceinline__ void unscaled(const TxEntry &e, const uint8_t *data, Rgba8 color) {
         const int c = col - ((int)floorf(e.x) + (int)e.x_offset), r = row - ((int)floorf(e.y) + (int)e.y_offset);
         if (c < 0 || c >= (int)e.width || r < 0 || r >= (int)e.height) return;
         if (tx_bit(data + e.bitmap_offset, (int)e.height * (int)e.bytes_per_row, r, c, e.bytes_per_row)) pixel(color);
@@ -242,7 +219,7 @@ template <int PIX> struct Tx {
         if (end < 0.0f) return false; // the cast the reference leaves undefined: the bit writes nothing
         return p >= (int)start && p < (int)end;
     }
-    __device__ __forceinline__ void fast_scaled(const TxEntry &e, const uint8_t *data, TxRgba color, float scale, float4 clip) {
+    __device__ __forceinline__ void fast_scaled(const TxEntry &e, const uint8_t *data, Rgba8 color, float scale, float4 clip) {
         int r0, r1, c0, c1;
         candidates((float)row, e.y, scale, e.y_offset, e.height, r0, r1);
         candidates((float)col, e.x, scale, e.x_offset, e.width, c0, c1);
@@ -268,8 +245,8 @@ template <int PIX> struct Tx {
         for (float row_f = row_start_f; row_f <= row_end_f; row_f += 1.0f) {
             for (float col_f = col_start_f; col_f <= col_end_f; col_f += 1.0f) {
                 if (!tx_bit(char_data, len, (int)row_f, (int)col_f, e.bytes_per_row)) continue;
-                const float overlap_x = tx_clamp(fminf(x1, col_f + 1.0f) - fmaxf(x0, col_f), 0.0f, 1.0f);
-                const float overlap_y = tx_clamp(fminf(y1, row_f + 1.0f) - fmaxf(y0, row_f), 0.0f, 1.0f);
+                const float overlap_x = clampf(fminf(x1, col_f + 1.0f) - fmaxf(x0, col_f), 0.0f, 1.0f);
+                const float overlap_y = clampf(fminf(y1, row_f + 1.0f) - fmaxf(y0, row_f), 0.0f, 1.0f);
                 total_coverage += overlap_x * overlap_y;
             }
         }
@@ -279,7 +256,7 @@ template <int PIX> struct Tx {
     // dest = pen + d + offset * scale for d = 0, 1, ... below ceil(size * scale); the pixel is floor(dest) (setPoint; atOrNull's trunc gate
     // lets through nothing that floor does not: a coordinate in (-1, 0) passes the gate and is dropped by setPoint). The d that land on this
     // lane's pixel lie within two of p - floor(pen + offset * scale); each is tested with the reference's expression.
-    __device__ __forceinline__ void soft_scaled(const TxEntry &e, const uint8_t *data, TxRgba color, float scale) {
+    __device__ __forceinline__ void soft_scaled(const TxEntry &e, const uint8_t *data, Rgba8 color, float scale) {
         const float dest_width = ceilf((float)e.width * scale), dest_height = ceilf((float)e.height * scale);
         const float ox = (float)e.x_offset * scale, oy = (float)e.y_offset * scale;
         const float dx_mid = (float)col - floorf(e.x + ox), dy_mid = (float)row - floorf(e.y + oy);
@@ -290,7 +267,7 @@ template <int PIX> struct Tx {
             for (float dx = fmaxf(dx_mid - 2.0f, 0.0f); dx <= dx_mid + 2.0f && dx < dest_width; dx += 1.0f) {
                 if (floorf(e.x + dx + ox) != (float)col) continue;
                 const float normalized_coverage = coverage(e, char_data, len, dx, dy, scale);
-                if (normalized_coverage > 0) pixel(tx_fade(color, normalized_coverage));
+                if (normalized_coverage > 0) pixel(fade(color, normalized_coverage));
             }
         }
     }
@@ -298,76 +275,24 @@ template <int PIX> struct Tx {
 
 template <int PIX>
 __global__ __launch_bounds__(256) void k_text(DImg img, zg_font font, const zg_text_cmd *cmds, const TxEntry *entries, const float4 *clips, const uint32_t *total) {
-    using P = Px<PIX>;
-    __shared__ uint16_t s_list[TX_CHUNK];
-    __shared__ int s_wave_count[TX_CHUNK / 64];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx0 = (int)blockIdx.x * TX_TILE, ty0 = (int)blockIdx.y * TX_TILE;
+    const int tx0 = (int)blockIdx.x * CV_TILE, ty0 = (int)blockIdx.y * CV_TILE;
     Tx<PIX> tx;
-    tx.col = tx0 + (tid & 15); tx.row = ty0 + (tid >> 4);
-    tx.inside = tx.col < img.cols && tx.row < img.rows;
-    tx.dirty = false;
-    tx.px = P::zero();
-    const size_t index = (size_t)tx.row * img.stride + (size_t)tx.col;
-    bool loaded = false;
-    const uint32_t n = *total;
-    for (uint32_t base = 0; base < n; base += TX_CHUNK) {
-        bool hit[TX_CHUNK / 256];
-        unsigned long long ballot[TX_CHUNK / 256];
-#pragma unroll
-        for (int j = 0; j < TX_CHUNK / 256; ++j) {
-            const uint32_t i = base + 256u * j + (uint32_t)tid;
-            hit[j] = false;
-            if (i < n) {
-                const ushort4 b = entries[i].box;
-                hit[j] = (int)b.x < tx0 + TX_TILE && (int)b.z > tx0 && (int)b.y < ty0 + TX_TILE && (int)b.w > ty0;
-            }
-            ballot[j] = __ballot(hit[j]);
-            if (lane == 0) s_wave_count[4 * j + wave] = __popcll(ballot[j]);
-        }
-        __syncthreads();
-        int found = 0; // list position = the entries of earlier slices, then of earlier waves of this slice, then of earlier lanes
-#pragma unroll
-        for (int j = 0; j < TX_CHUNK / 256; ++j) {
-            int before = found;
-            for (int w = 0; w < 4; ++w) {
-                const int cnt = s_wave_count[4 * j + w];
-                if (w < wave) before += cnt;
-                found += cnt;
-            }
-            if (hit[j]) s_list[before + __popcll(ballot[j] & ((1ull << lane) - 1ull))] = (uint16_t)(256 * j + tid);
-        }
-        __syncthreads();
-        if (found > 0 && !loaded) {
-            if (tx.inside) tx.px = P::load(img.data, index);
-            loaded = true;
-        }
-        for (int k = 0; k < found; ++k) {
-            const uint32_t ei = base + (uint32_t)__builtin_amdgcn_readfirstlane((int)s_list[k]);
-            const TxEntry e = entries[ei];
+    tx.place(img);
+    tile_gather<PIX>(
+        img, tx, *total, [&](uint32_t i) { return tile_meets_box(entries[i].box, tx0, ty0); },
+        [&](uint32_t i) {
+            const TxEntry e = entries[i];
             const zg_text_cmd c = cmds[e.cmd];
-            if (!tx.inside) continue;
+            if (!tx.inside) return;
             const ushort4 b = e.box;
-            if (tx.col < (int)b.x || tx.col >= (int)b.z || tx.row < (int)b.y || tx.row >= (int)b.w) continue;
-            TxRgba color;
-            color[0] = c.color[0]; color[1] = c.color[1]; color[2] = c.color[2]; color[3] = c.color[3];
+            if (tx.col < (int)b.x || tx.col >= (int)b.z || tx.row < (int)b.y || tx.row >= (int)b.w) return;
+            const Rgba8 color = rgba_of(c.color);
             if (c.scale == 1.0f) tx.unscaled(e, font.data, color);
             else if (c.mode == ZG_DRAW_FAST) tx.fast_scaled(e, font.data, color, c.scale, clips[e.cmd]);
             else tx.soft_scaled(e, font.data, color, c.scale);
-        }
-        __syncthreads();
-    }
-    if (tx.dirty && tx.inside) P::store(img.data, index, tx.px);
+        });
 }
 
-static int check_text_image(const zg_image *img, bool device_pointer) {
-    if (const int rc = check_image(img, "img", device_pointer)) return rc;
-    ZG_REQUIRE(img->pixel == ZG_PIXEL_U8 || img->pixel == ZG_PIXEL_RGB_U8 || img->pixel == ZG_PIXEL_RGBA_U8, ZG_ERR_UNSUPPORTED,
-               "canvas_draw_text: pixel type %d (u8, Rgb(u8) and Rgba(u8) are drawn on)", img->pixel);
-    ZG_REQUIRE(img->rows <= ZG_CANVAS_MAX_SIZE && img->cols <= ZG_CANVAS_MAX_SIZE, ZG_ERR_UNSUPPORTED, "canvas_draw_text: %u x %u image (at most %u each way)",
-               img->rows, img->cols, ZG_CANVAS_MAX_SIZE);
-    return ZG_OK;
-}
 static int check_text_args(const zg_font *font, const zg_text_cmd *cmds, uint32_t n, const uint32_t *codepoints, uint32_t n_codepoints) {
     ZG_REQUIRE(font != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_text: null font");
     ZG_REQUIRE(font->data_len == 0 || font->data != nullptr, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_text: null font data");
@@ -393,13 +318,9 @@ static int text_draw(const zg_image *img, const zg_font &font, const zg_text_cmd
     if ((rc = sc.alloc())) return rc;
     k_text_prep<<<ceil_div(n, 256), 256, 0, s>>>(font, cmds, n, count_device, codepoints, n_codepoints, (int)img->rows, (int)img->cols, entries, clips, total);
     if ((rc = launch_ok("k_text_prep"))) return rc;
-    const dim3 grid(ceil_div(img->cols, TX_TILE), ceil_div(img->rows, TX_TILE));
+    const dim3 grid = tile_grid(img);
     const DImg d = dimg(img);
-    switch (img->pixel) {
-    case ZG_PIXEL_U8: k_text<ZG_PIXEL_U8><<<grid, 256, 0, s>>>(d, font, cmds, entries, clips, total); break;
-    case ZG_PIXEL_RGB_U8: k_text<ZG_PIXEL_RGB_U8><<<grid, 256, 0, s>>>(d, font, cmds, entries, clips, total); break;
-    default: k_text<ZG_PIXEL_RGBA_U8><<<grid, 256, 0, s>>>(d, font, cmds, entries, clips, total); break;
-    }
+    dispatch_u8_pixel(img->pixel, [&](auto pix) { k_text<decltype(pix)::value><<<grid, 256, 0, s>>>(d, font, cmds, entries, clips, total); });
     return launch_ok("k_text");
 }
 
@@ -477,14 +398,14 @@ int zg_text_bounds_host(const zg_font *host_font, const uint32_t *codepoints, ui
 
 int zg_canvas_draw_text(const zg_image *img, const zg_font *font, const zg_text_cmd *cmds, uint32_t n, const uint32_t *count_device, const uint32_t *codepoints,
                         uint32_t n_codepoints, zg_stream stream) {
-    if (const int rc = check_text_image(img, true)) return rc;
+    if (const int rc = check_draw_image(img, true, "canvas_draw_text")) return rc;
     if (const int rc = check_text_args(font, cmds, n, codepoints, n_codepoints)) return rc;
     ZG_REQUIRE(font->glyphs != nullptr || font->n_glyphs == 0, ZG_ERR_INVALID_ARGUMENT, "canvas_draw_text: %u glyphs and no table", font->n_glyphs);
     return text_draw(img, *font, cmds, n, count_device, codepoints, n_codepoints, as_stream(stream));
 }
 
 int zg_canvas_draw_text_host(const zg_image *img, const zg_font *host_font, const zg_text_cmd *cmds, uint32_t n, const uint32_t *codepoints, uint32_t n_codepoints) {
-    if (const int rc = check_text_image(img, false)) return rc;
+    if (const int rc = check_draw_image(img, false, "canvas_draw_text")) return rc;
     if (const int rc = check_text_args(host_font, cmds, n, codepoints, n_codepoints)) return rc;
     if (const int rc = zg_font_check(host_font)) return rc;
     uint64_t running = 0;

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .image import Image, _is_torch, torch
+from .image import Image, torch
 
 # zg_text_cmd and zg_glyph as numpy structured dtypes: the bytes of the C structs
 TEXT_CMD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("scale", "<f4"), ("mode", "<i4"), ("color", "u1", (4,)), ("first_codepoint", "<u4"),
@@ -139,14 +139,11 @@ def draw_text(image, font: BitmapFont, cmds, codepoints, count=None, n=None) -> 
     holds), `codepoints` a device tensor of 32-bit codepoints, `count` an optional device tensor whose first 4 bytes are the number of
     commands to execute. Asynchronous on the current stream; nothing is synchronised, copied or uploaded once the font is on the device."""
     img = image if isinstance(image, Image) else Image(image)
-    if not img.on_device or not _is_torch(cmds) or not _is_torch(codepoints) or (count is not None and not _is_torch(count)):
-        raise ValueError("draw_text takes a device image and device tensors")
+    from .canvas import _device_lists
+
+    n = _device_lists("draw_text", img, cmds, TEXT_CMD_DTYPE.itemsize, n, count, codepoints)
     if codepoints.element_size() != 4 or not codepoints.is_contiguous():
         raise ValueError("codepoints must be a contiguous tensor of 32-bit integers")
-    cap = cmds.numel() * cmds.element_size() // TEXT_CMD_DTYPE.itemsize
-    n = cap if n is None else int(n)
-    if n > cap or (count is not None and count.numel() * count.element_size() < 4):
-        raise ValueError("cmds or count tensor too small")
     ncp = codepoints.numel()
     dfont = font._device_font(img.data.device)
     d = img._desc()
