@@ -759,4 +759,8 @@ ZG_API void zg_jpeg_free(void *p);
  * them: a module of its own in the same way (_FDM_SIGNATURES, zig/zignal_hip_fdm.zig). */
 #include "zignal_hip_fdm.h"
 
+/* Tracer (src/features/Tracer.zig): edge maps to polylines, and the builder from polylines to Canvas line commands: a module of its own
+ * in the same way (_TRACER_SIGNATURES, zig/zignal_hip_tracer.zig). */
+#include "zignal_hip_tracer.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -546,6 +546,22 @@ _FDM_RESTYPES = {"zg_fdm_sizeof_moments": C.c_size_t, "zg_fdm_sizeof_target": C.
 FDM_EXPORTED_SYMBOLS = tuple(_FDM_SIGNATURES)
 
 
+class ZgTracerOptions(C.Structure):
+    """zg_tracer_options == Tracer's two fields (src/features/Tracer.zig:20-25)."""
+    _fields_ = [("min_path_length", C.c_uint32), ("simplification_epsilon", C.c_float)]
+
+
+# the Tracer module: every symbol include/zignal_hip_tracer.h declares
+_TRACER_SIGNATURES = {
+    "zg_trace_scratch_bytes": [C.c_uint32, C.c_uint32],
+    "zg_trace_paths": [_IMG, C.POINTER(ZgTracerOptions), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_trace_paths_host": [_IMG, C.POINTER(ZgTracerOptions), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _U32P],
+    "zg_canvas_cmds_from_paths": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+_TRACER_RESTYPES = {"zg_trace_scratch_bytes": C.c_size_t}
+TRACER_EXPORTED_SYMBOLS = tuple(_TRACER_SIGNATURES)
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -557,7 +573,8 @@ def lib() -> C.CDLL:
         for table, restypes in ((_SIGNATURES, _RESTYPES), (_ORB_SIGNATURES, _ORB_RESTYPES), (_MATCH_SIGNATURES, _MATCH_RESTYPES),
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
                                 (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
-                                (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES)):
+                                (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES),
+                                (_TRACER_SIGNATURES, _TRACER_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

@@ -162,6 +162,19 @@ def cmds_from_keypoints(keypoints, count, radius: float, color, width: int = 1, 
     return cmds_out, count_out
 
 
+def cmds_from_paths(points, path_offsets, counts, color, width: int = 1, mode="fast", cmds_out=None, count_out=None):
+    """zg_canvas_cmds_from_paths: one line command per consecutive pair of points of every path Tracer.trace_into wrote (`points`,
+    `path_offsets`, `counts`: its three device tensors). cmds_out defaults to room for one command per point, which no list of paths
+    exceeds. Returns (cmds, count) device tensors for draw(); asynchronous on the current stream."""
+    cap, cmds_out, count_out = _builder_out(points, 8, cmds_out, count_out)
+    col = (C.c_uint8 * 4)(*_color(color))
+    with torch.cuda.device(points.device):
+        stream = C.c_void_p(torch.cuda.current_stream(points.device).cuda_stream)
+        L.check(L.lib().zg_canvas_cmds_from_paths(C.c_void_p(points.data_ptr()), C.c_void_p(path_offsets.data_ptr()), C.c_void_p(counts.data_ptr()), cap, col,
+                                                  int(width), _mode(mode), C.c_void_p(cmds_out.data_ptr()), C.c_void_p(count_out.data_ptr()), stream))
+    return cmds_out, count_out
+
+
 class Canvas:
     """Canvas(T): the draw methods append to a command list, flush() executes it into the image in list order and empties it."""
 

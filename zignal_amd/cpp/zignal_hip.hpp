@@ -1299,4 +1299,66 @@ template <typename T, template <typename> class Img = Image> class FeatureDistri
     bool has_target_ = false;
 };
 
+// ---- features: Tracer (src/features/Tracer.zig) ----
+// The reference's two fields and defaults; trace returns its list of paths, each a list of (x = col, y = row) points, bit for bit.
+struct Tracer {
+    uint32_t min_path_length = 5;
+    float simplification_epsilon = 1.0f;
+    using Path = std::vector<Point2>;
+
+    zg_tracer_options c_options() const { return zg_tracer_options{min_path_length, simplification_epsilon}; }
+
+    // host image: the counts first, then the lists (two synchronous calls)
+    std::vector<Path> trace(const Image<uint8_t> &edges) const {
+        const zg_image s = edges.desc();
+        const zg_tracer_options o = c_options();
+        uint32_t counts[4] = {0, 0, 0, 0};
+        check(zg_trace_paths_host(&s, &o, nullptr, 0, nullptr, 0, counts));
+        std::vector<Point2> points(counts[1]);
+        std::vector<uint32_t> offsets((size_t)counts[0] + 1);
+        check(zg_trace_paths_host(&s, &o, points.empty() ? nullptr : &points[0].x, counts[1], offsets.data(), counts[0], counts));
+        return split(points, offsets);
+    }
+    // device image, lists back on the host: the counts first, then device scratch of exactly that size. Synchronises the image's stream.
+    std::vector<Path> trace(const DeviceImage<uint8_t> &edges) const {
+        void *mem = nullptr;
+        check(zg_malloc(&mem, 32));
+        uint32_t counts[4] = {0, 0, 0, 0};
+        int rc = traceIntoStatus(edges, nullptr, 0, (uint32_t *)mem + 4, 0, (uint32_t *)mem);
+        if (rc == ZG_OK) rc = zg_memcpy_d2h(counts, mem, sizeof counts, edges.stream());
+        (void)zg_free(mem);
+        check(rc);
+        const size_t point_bytes = ((size_t)counts[1] * sizeof(Point2) + 255) / 256 * 256, offset_bytes = ((size_t)counts[0] + 1) * 4;
+        check(zg_malloc(&mem, point_bytes + offset_bytes + 16));
+        uint32_t *doffsets = (uint32_t *)((char *)mem + point_bytes), *dcounts = doffsets + counts[0] + 1;
+        std::vector<Point2> points(counts[1]);
+        std::vector<uint32_t> offsets((size_t)counts[0] + 1);
+        rc = traceIntoStatus(edges, counts[1] ? (Point2 *)mem : nullptr, counts[1], doffsets, counts[0], dcounts);
+        if (rc == ZG_OK) rc = zg_memcpy_d2h(offsets.data(), doffsets, offset_bytes, edges.stream());
+        if (rc == ZG_OK && counts[1]) rc = zg_memcpy_d2h(points.data(), mem, (size_t)counts[1] * sizeof(Point2), edges.stream());
+        (void)zg_free(mem);
+        check(rc);
+        return split(points, offsets);
+    }
+    // asynchronous device form (zg_trace_paths): points, path_offsets (path_capacity + 1 words) and counts (four words) are device memory
+    void traceInto(const DeviceImage<uint8_t> &edges, Point2 *points, uint32_t point_capacity, uint32_t *path_offsets, uint32_t path_capacity,
+                   uint32_t *counts) const {
+        check(traceIntoStatus(edges, points, point_capacity, path_offsets, path_capacity, counts));
+    }
+
+  private:
+    int traceIntoStatus(const DeviceImage<uint8_t> &edges, Point2 *points, uint32_t point_capacity, uint32_t *path_offsets, uint32_t path_capacity,
+                        uint32_t *counts) const {
+        const zg_image s = edges.desc();
+        const zg_tracer_options o = c_options();
+        return zg_trace_paths(&s, &o, points ? &points->x : nullptr, point_capacity, path_offsets, path_capacity, counts, edges.stream());
+    }
+    static std::vector<Path> split(const std::vector<Point2> &points, const std::vector<uint32_t> &offsets) {
+        std::vector<Path> paths(offsets.size() - 1);
+        for (size_t i = 0; i + 1 < offsets.size(); ++i) paths[i].assign(points.begin() + offsets[i], points.begin() + offsets[i + 1]);
+        return paths;
+    }
+};
+static_assert(sizeof(Point2) == 8, "a traced point is two f32");
+
 } // namespace zignal

@@ -18,6 +18,7 @@
 //   k_flood_fill    a pixel is written iff find(p) == find(seed); one atomic add per workgroup counts them.
 // Distances (pixelDistance, :28-51) take no square root here: the host turns the threshold into one constant (bound() below).
 #include "zg_common.h"
+#include "zg_internal.h"
 #include "zg_unionfind.h"
 
 #include <cmath>
@@ -345,16 +346,7 @@ int flood(const zg_image *img, uint32_t row, uint32_t col, const uint32_t *seed_
         return launch_ok("k_flood_links");
     });
     if (rc) return rc;
-    const unsigned tiles_x = ceil_div(img->cols, (unsigned)FT), tiles_y = ceil_div(img->rows, (unsigned)FT);
-    hipLaunchKernelGGL(k_flood_tile, dim3(tiles_x * tiles_y), dim3(256), 0, s, (const uint8_t *)a.links, a.label, a.rows, a.cols, (int)tiles_x);
-    if ((rc = launch_ok("k_flood_tile"))) return rc;
-    const unsigned nvb = tiles_x - 1, nhb = tiles_y - 1;
-    const size_t border = (size_t)nvb * img->rows + (size_t)nhb * img->cols;
-    if (border) {
-        hipLaunchKernelGGL(k_flood_border, dim3((unsigned)((border + 255) / 256)), dim3(256), 0, s, (const uint8_t *)a.links, a.label, a.rows, a.cols, (int)nvb,
-                           (int)nhb);
-        if ((rc = launch_ok("k_flood_border"))) return rc;
-    }
+    if ((rc = flood_label_components(a.links, a.label, img->rows, img->cols, s))) return rc;
     return dispatch_pixel(img->pixel, [&](auto tag) {
         constexpr int PIX = decltype(tag)::value;
         const unsigned per = PIX == ZG_PIXEL_U8 ? 4 : 1;
@@ -364,6 +356,23 @@ int flood(const zg_image *img, uint32_t row, uint32_t col, const uint32_t *seed_
 }
 
 } // namespace
+
+// k_flood_tile and k_flood_border over a plane of link bytes (zg_internal.h): what flood() above runs, and tracer.hip on the links of an edge map
+int flood_label_components(const uint8_t *links, int *label, uint32_t rows, uint32_t cols, hipStream_t s) {
+    int rc;
+    const unsigned tiles_x = ceil_div(cols, (unsigned)FT), tiles_y = ceil_div(rows, (unsigned)FT);
+    hipLaunchKernelGGL(k_flood_tile, dim3(tiles_x * tiles_y), dim3(256), 0, s, links, label, (int)rows, (int)cols, (int)tiles_x);
+    if ((rc = launch_ok("k_flood_tile"))) return rc;
+    const unsigned nvb = tiles_x - 1, nhb = tiles_y - 1;
+    const size_t border = (size_t)nvb * rows + (size_t)nhb * cols;
+    if (border) {
+        hipLaunchKernelGGL(k_flood_border, dim3((unsigned)((border + 255) / 256)), dim3(256), 0, s, links, label, (int)rows, (int)cols, (int)nvb,
+                           (int)nhb);
+        if ((rc = launch_ok("k_flood_border"))) return rc;
+    }
+    return ZG_OK;
+}
+
 } // namespace zg
 
 using namespace zg;

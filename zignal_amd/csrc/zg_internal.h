@@ -111,4 +111,9 @@ int try_pyramid_level_u8(const zg_image *src, const zg_image *level, const int32
 int fast_detect_compact(const zg_image *images, uint32_t n, const uint32_t *thresholds, uint32_t *const *pos, uint32_t *const *key,
                         const uint32_t *capacities, uint32_t *const *counts, hipStream_t s);
 
+// ---- flood.hip: the component labelling of a plane of link bytes (bit 0 E, 1 S, 2 SE, 3 SW: the links a pixel owns), for tracer.hip.
+// label: rows * cols ints; afterwards label[p] is p's parent in a forest whose roots are the smallest index of each component.
+int flood_label_components(const uint8_t *links, int *label, uint32_t rows, uint32_t cols, hipStream_t s);
+constexpr uint8_t FLOOD_LINK_E = 1, FLOOD_LINK_S = 2, FLOOD_LINK_SE = 4, FLOOD_LINK_SW = 8;
+
 } // namespace zg
