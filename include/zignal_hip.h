@@ -763,4 +763,8 @@ ZG_API void zg_jpeg_free(void *p);
  * in the same way (_TRACER_SIGNATURES, zig/zignal_hip_tracer.zig). */
 #include "zignal_hip_tracer.h"
 
+/* The QR detector (src/qrcode/detector.zig): a frame to sampled module grids and their corners, and the builder from those corners to
+ * Canvas line commands: a module of its own in the same way (_QR_SIGNATURES, zig/zignal_hip_qr.zig). */
+#include "zignal_hip_qr.h"
+
 #endif /* ZIGNAL_HIP_H */

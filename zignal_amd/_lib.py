@@ -562,6 +562,46 @@ _TRACER_RESTYPES = {"zg_trace_scratch_bytes": C.c_size_t}
 TRACER_EXPORTED_SYMBOLS = tuple(_TRACER_SIGNATURES)
 
 
+class ZgQrFinder(C.Structure):
+    """zg_qr_finder == FinderPattern (src/qrcode/detector.zig:170-175)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("module_size", C.c_float), ("hits", C.c_float)]
+
+
+class ZgQrFourth(C.Structure):
+    """zg_qr_fourth == Fourth (detector.zig:410-413)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("is_alignment", C.c_uint32)]
+
+
+class ZgQrDetection(C.Structure):
+    """zg_qr_detection: every intermediate result of detectAndDecode (detector.zig:86-156)."""
+    _fields_ = [("finders", ZgQrFinder * 64), ("finder_count", C.c_uint32), ("merged_count", C.c_uint32), ("triple_found", C.c_uint32),
+                ("triple", ZgQrFinder * 3), ("version_estimate", C.c_uint32), ("version_count", C.c_uint32), ("versions", C.c_uint8 * 8),
+                ("fourth_count", C.c_uint32), ("fourths", ZgQrFourth * 5), ("grids_total", C.c_uint32), ("grids_written", C.c_uint32),
+                ("modules_written", C.c_uint32)]
+
+
+class ZgQrGrid(C.Structure):
+    """zg_qr_grid: one trial that passed the timing check and sampleGrid."""
+    _fields_ = [("version", C.c_uint32), ("dim", C.c_uint32), ("fourth_index", C.c_uint32), ("modules_offset", C.c_uint32), ("version_hint", C.c_int32),
+                ("corners", C.c_float * 8), ("reserved", C.c_uint32), ("transform", C.c_double * 9)]
+
+
+QR_ADAPTIVE, QR_OTSU, QR_BINARY = 0, 1, 2
+QR_MAX_MODULES = 177 * 177
+
+# the QR module: every symbol include/zignal_hip_qr.h declares
+_QR_SIGNATURES = {
+    "zg_qr_sizeof_detection": [],
+    "zg_qr_sizeof_grid": [],
+    "zg_qr_scratch_bytes": [C.c_uint32, C.c_uint32],
+    "zg_qr_detect": [_IMG, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "zg_qr_detect_host": [_IMG, C.c_int, C.POINTER(ZgQrDetection), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32],
+    "zg_canvas_cmds_from_qr": [C.c_void_p, C.c_void_p, C.c_uint32, _U8P, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+_QR_RESTYPES = {"zg_qr_sizeof_detection": C.c_size_t, "zg_qr_sizeof_grid": C.c_size_t, "zg_qr_scratch_bytes": C.c_size_t}
+QR_EXPORTED_SYMBOLS = tuple(_QR_SIGNATURES)
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -574,7 +614,7 @@ def lib() -> C.CDLL:
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
                                 (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
                                 (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES),
-                                (_TRACER_SIGNATURES, _TRACER_RESTYPES)):
+                                (_TRACER_SIGNATURES, _TRACER_RESTYPES), (_QR_SIGNATURES, _QR_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes
@@ -587,6 +627,9 @@ def lib() -> C.CDLL:
             if getattr(l, name)() != C.sizeof(struct):
                 raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
         for name, struct in (("zg_fdm_sizeof_moments", ZgFdmMoments), ("zg_fdm_sizeof_target", ZgFdmTarget), ("zg_fdm_sizeof_transform", ZgFdmTransform)):
+            if getattr(l, name)() != C.sizeof(struct):
+                raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
+        for name, struct in (("zg_qr_sizeof_detection", ZgQrDetection), ("zg_qr_sizeof_grid", ZgQrGrid)):
             if getattr(l, name)() != C.sizeof(struct):
                 raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
         _lib = l

@@ -175,6 +175,19 @@ def cmds_from_paths(points, path_offsets, counts, color, width: int = 1, mode="f
     return cmds_out, count_out
 
 
+def cmds_from_qr(grids, detection, color, width: int = 1, mode="fast", cmds_out=None, count_out=None):
+    """zg_canvas_cmds_from_qr: four line commands per grid QrDetector.detect_into wrote (`grids`, `detection`: its device tensors),
+    outlining the symbol's corners. cmds_out defaults to room for four commands per grid record `grids` can hold. Returns (cmds, count)
+    device tensors for draw(); asynchronous on the current stream."""
+    cap, cmds_out, count_out = _builder_out(grids, 32, cmds_out, count_out)  # a grid record is 128 bytes and gives four commands
+    col = (C.c_uint8 * 4)(*_color(color))
+    with torch.cuda.device(grids.device):
+        stream = C.c_void_p(torch.cuda.current_stream(grids.device).cuda_stream)
+        L.check(L.lib().zg_canvas_cmds_from_qr(C.c_void_p(grids.data_ptr()), C.c_void_p(detection.data_ptr()), cap, col, int(width), _mode(mode),
+                                               C.c_void_p(cmds_out.data_ptr()), C.c_void_p(count_out.data_ptr()), stream))
+    return cmds_out, count_out
+
+
 class Canvas:
     """Canvas(T): the draw methods append to a command list, flush() executes it into the image in list order and empties it."""
 

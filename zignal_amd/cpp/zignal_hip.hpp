@@ -1361,4 +1361,95 @@ struct Tracer {
 };
 static_assert(sizeof(Point2) == 8, "a traced point is two f32");
 
+// ---- qrcode: the detector (src/qrcode/detector.zig:57-641) ----
+// A frame to the sampled module grids and their corners, which are what the reference hands to decoder.decodeModules, in the reference's
+// order of trial, bit for bit. Decoding the grids is host work outside this library.
+struct QrGrid {
+    int binarize = 0;          // the pass that produced it: ZG_QR_ADAPTIVE, ZG_QR_OTSU or ZG_QR_BINARY
+    uint32_t version = 0, dim = 0, fourth_index = 0;
+    int32_t version_hint = -1; // decoder.readVersion of this grid for version >= 7
+    float corners[8] = {};     // top left, top right, bottom left, bottom right, (x, y) each
+    double transform[9] = {};  // module space to image space, row-major
+    std::vector<uint8_t> modules; // dim * dim, 0 or 1
+};
+
+struct QrDetector {
+    // host image, one binarisation: the counts first, then the lists (two synchronous calls). The record of every stage comes back.
+    template <typename T> zg_qr_detection detectPass(const Image<T> &image, int binarize, std::vector<QrGrid> &out) const {
+        const zg_image s = image.desc();
+        zg_qr_detection det;
+        check(zg_qr_detect_host(&s, binarize, &det, nullptr, 0, nullptr, 0));
+        const uint32_t n = det.grids_total;
+        std::vector<zg_qr_grid> grids(n);
+        std::vector<uint8_t> modules((size_t)n * ZG_QR_MAX_MODULES);
+        check(zg_qr_detect_host(&s, binarize, &det, n ? grids.data() : nullptr, n, n ? modules.data() : nullptr, n * ZG_QR_MAX_MODULES));
+        append(out, grids, modules, det.grids_written, binarize);
+        return det;
+    }
+    // device image, lists back on the host: the counts first, then device scratch of exactly that size. Synchronises the image's stream.
+    template <typename T> zg_qr_detection detectPass(const DeviceImage<T> &image, int binarize, std::vector<QrGrid> &out) const {
+        void *mem = nullptr;
+        check(zg_malloc(&mem, sizeof(zg_qr_detection)));
+        zg_qr_detection det;
+        int rc = detectIntoStatus(image, binarize, (zg_qr_detection *)mem, nullptr, 0, nullptr, 0);
+        if (rc == ZG_OK) rc = zg_memcpy_d2h(&det, mem, sizeof det, image.stream());
+        (void)zg_free(mem);
+        check(rc);
+        const uint32_t n = det.grids_total;
+        const size_t grid_bytes = ((size_t)n * sizeof(zg_qr_grid) + 255) / 256 * 256, module_bytes = ((size_t)n * ZG_QR_MAX_MODULES + 255) / 256 * 256;
+        check(zg_malloc(&mem, grid_bytes + module_bytes + sizeof(zg_qr_detection)));
+        zg_qr_grid *dgrids = (zg_qr_grid *)mem;
+        uint8_t *dmodules = (uint8_t *)mem + grid_bytes;
+        zg_qr_detection *ddet = (zg_qr_detection *)((char *)mem + grid_bytes + module_bytes);
+        std::vector<zg_qr_grid> grids(n);
+        std::vector<uint8_t> modules((size_t)n * ZG_QR_MAX_MODULES);
+        rc = detectIntoStatus(image, binarize, ddet, n ? dgrids : nullptr, n, n ? dmodules : nullptr, n * ZG_QR_MAX_MODULES);
+        if (rc == ZG_OK) rc = zg_memcpy_d2h(&det, ddet, sizeof det, image.stream());
+        if (rc == ZG_OK && det.grids_written) rc = zg_memcpy_d2h(grids.data(), dgrids, (size_t)det.grids_written * sizeof(zg_qr_grid), image.stream());
+        if (rc == ZG_OK && det.modules_written) rc = zg_memcpy_d2h(modules.data(), dmodules, det.modules_written, image.stream());
+        (void)zg_free(mem);
+        check(rc);
+        append(out, grids, modules, det.grids_written, binarize);
+        return det;
+    }
+    // The adaptive pass's grids followed by the Otsu pass's (detector.zig:71-82), each tagged with its pass: the reference runs the second
+    // pass only when nothing of the first decoded, so a decoder walking this list in order reproduces it.
+    template <typename Img> std::vector<QrGrid> detect(const Img &image) const {
+        std::vector<QrGrid> out;
+        detectPass(image, ZG_QR_ADAPTIVE, out);
+        detectPass(image, ZG_QR_OTSU, out);
+        return out;
+    }
+    // asynchronous device form (zg_qr_detect): detection, grids and modules are device memory
+    template <typename T>
+    void detectInto(const DeviceImage<T> &image, int binarize, zg_qr_detection *detection, zg_qr_grid *grids, uint32_t grid_capacity, uint8_t *modules,
+                    uint32_t module_capacity) const {
+        check(detectIntoStatus(image, binarize, detection, grids, grid_capacity, modules, module_capacity));
+    }
+
+  private:
+    template <typename T>
+    int detectIntoStatus(const DeviceImage<T> &image, int binarize, zg_qr_detection *detection, zg_qr_grid *grids, uint32_t grid_capacity, uint8_t *modules,
+                         uint32_t module_capacity) const {
+        const zg_image s = image.desc();
+        return zg_qr_detect(&s, binarize, detection, grids, grid_capacity, modules, module_capacity, image.stream());
+    }
+    static void append(std::vector<QrGrid> &out, const std::vector<zg_qr_grid> &grids, const std::vector<uint8_t> &modules, uint32_t written, int binarize) {
+        for (uint32_t i = 0; i < written; ++i) {
+            const zg_qr_grid &g = grids[i];
+            QrGrid q;
+            q.binarize = binarize;
+            q.version = g.version;
+            q.dim = g.dim;
+            q.fourth_index = g.fourth_index;
+            q.version_hint = g.version_hint;
+            std::memcpy(q.corners, g.corners, sizeof q.corners);
+            std::memcpy(q.transform, g.transform, sizeof q.transform);
+            q.modules.assign(modules.begin() + g.modules_offset, modules.begin() + g.modules_offset + (size_t)g.dim * g.dim);
+            out.push_back(q);
+        }
+    }
+};
+static_assert(sizeof(zg_qr_detection) == 1176 && sizeof(zg_qr_grid) == 128, "the detector's two records");
+
 } // namespace zignal
