@@ -155,8 +155,10 @@ def test_gaussian_blur_host_and_device_layers(oracle, kind, sigma):
 @pytest.mark.parametrize("kind", ("u8", "rgb_u8"))
 @pytest.mark.parametrize("border", BORDERS)
 def test_byte_stream_fast_path(oracle, kind, border):
-    """Grey / Rgb u8 rows whose byte length is a multiple of 16 run on the 16-bytes-per-lane kernel (conv_sep_bytes.hip):
-    non-negative integer taps summing to <= 257, 3..9 taps; tile seams at 1024 bytes, edges resolved per pixel."""
+    """Grey / Rgb u8 rows whose byte length is a multiple of 16 run on the 16-bytes-per-lane kernels: the 70 x 1040 and 33 x 2064 Rgb
+    frames on the stream kernel (conv_sep_stream.hip, tried first), every grey frame and the frames of fewer than 16 rows on the
+    LDS-tiled one (conv_sep_bytes.hip). Non-negative integer taps summing to <= 257, 3..9 taps; strip / tile seams at 1024 bytes,
+    edges resolved per pixel."""
     rng = np.random.default_rng(11)
     for n in (3, 5, 7, 9):
         t = rng.integers(0, 60, n)

@@ -36,21 +36,13 @@
 
 namespace zg {
 
-struct StreamArgs {
-    const uint8_t *src;
-    uint8_t *dst;
-    uint64_t src_pitch, dst_pitch; // bytes between rows
-    uint64_t src_frame, dst_frame; // bytes between frames
-    int32_t rows, row_bytes;       // source rows, bytes per source row
-    int32_t strips_x, strips_y;    // work items per frame
-    int32_t strip_rows;            // source rows per strip (even)
-    int32_t border;
-    uint32_t src_span, dst_span;   // bytes from a frame's first byte to the end of its last row
-    int32_t fast_ok;               // both spans fit 32 bits: whole-frame descriptors may be used
 #ifdef ZG_STREAM_TRACE
-    unsigned long long *trace;     // tools/exp/stream_trace.hip: per wave {start, end} of the 100 MHz clock + shader cycles
-#endif
+struct StreamArgs : StripArgs {
+    unsigned long long *trace; // tools/exp/stream_trace.hip: per wave {start, end} of the 100 MHz clock + shader cycles
 };
+#else
+typedef StripArgs StreamArgs;
+#endif
 
 template <int S> __device__ __forceinline__ u16x2 row_pair_s(const uint32_t (&q0)[12], const uint32_t (&q1)[12]) {
     constexpr int d = S >> 2, o = S & 3;
@@ -62,25 +54,6 @@ template <int S0, int N, int I = 0> struct UnpackRowsS { // P[I] = position S0 +
         if constexpr (I < N) {
             P[I] = row_pair_s<S0 + I>(q0, q1);
             UnpackRowsS<S0, N, I + 1>::run(q0, q1, P);
-        }
-    }
-};
-template <int SP, int NK, int N, int T, int I> struct RowTapsS {
-    __device__ static __forceinline__ u16x2 run(const u16x2 (&P)[N], const TapsU8<NK> &kx, u16x2 acc) {
-        if constexpr (I == NK) return acc;
-        else {
-            const uint16_t k = (uint16_t)kx.k[I];
-            const u16x2 kk = {k, k};
-            acc += P[T + SP * I] * kk; // <= 65535 by the preconditions: exact
-            return RowTapsS<SP, NK, N, T, I + 1>::run(P, kx, acc);
-        }
-    }
-};
-template <int SP, int NK, int N, int T> struct RowBytesS {
-    __device__ static __forceinline__ void run(const u16x2 (&P)[N], const TapsU8<NK> &kx, u16x2 (&out)[16]) {
-        if constexpr (T < 16) {
-            out[T] = RowTapsS<SP, NK, N, T, 0>::run(P, kx, u16x2{0, 0});
-            RowBytesS<SP, NK, N, T + 1>::run(P, kx, out);
         }
     }
 };
@@ -418,36 +391,21 @@ template <int SP, int NK, bool CLAMP, bool DOWN2>
 static int launch_stream(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int border, hipStream_t s) {
     TapsU8<NK> kx, ky;
     for (int i = 0; i < NK; ++i) { kx.k[i] = (uint32_t)ix[i]; ky.k[i] = (uint32_t)iy[i]; }
-    const uint32_t rows = b.src->rows;
-    StreamArgs a;
-    a.src = (const uint8_t *)b.src->data;
-    a.dst = (uint8_t *)b.dst->data;
-    a.src_pitch = b.src->stride * SP; a.dst_pitch = b.dst->stride * SP;
-    a.src_frame = b.src_frame; a.dst_frame = b.dst_frame;
-    a.rows = (int32_t)rows;
-    a.row_bytes = (int32_t)(b.src->cols * (uint32_t)SP);
-    a.strips_x = (int32_t)ceil_div((unsigned)a.row_bytes, 1024u);
-    a.strip_rows = stream_strip_rows(b, (uint32_t)a.strips_x, NK / 2, NK / 2 + 1);
-    a.strips_y = (int32_t)ceil_div(rows, (unsigned)a.strip_rows);
-    a.border = border;
-    const uint64_t sspan = (uint64_t)(rows - 1) * a.src_pitch + (uint64_t)a.row_bytes;
-    const uint64_t dspan = DOWN2 ? (uint64_t)(rows / 2 - 1) * a.dst_pitch + (uint64_t)(a.row_bytes / 2) : (uint64_t)(rows - 1) * a.dst_pitch + (uint64_t)a.row_bytes;
-    a.fast_ok = sspan <= 0xffffffffu && dspan <= 0xffffffffu;
-    a.src_span = (uint32_t)sspan;
-    a.dst_span = (uint32_t)dspan;
-    const uint64_t items = (uint64_t)a.strips_x * a.strips_y * b.n;
-    if (items > 0x7fffffffu) return -1;
+    StreamArgs a{};
+    dim3 grid;
+    const int strip_rows = stream_strip_rows(b, strips_across(b.src, SP), NK / 2, NK / 2 + 1);
+    if (strip_args(a, grid, b, border, SP, SP, DOWN2, strip_rows, 0xffffffffu, false) != 0) return -1;
     // row taps symmetric with unit ends: the folded row pass (the CLAMP instantiations — tap sums past 256 — keep the plain one)
     static const bool no_fold = getenv("ZIGNAL_HIP_STREAM_NO_FOLD") != nullptr; // A/B hook of round 5, read once
     bool unit = ix[0] == 1 && iy[0] == 1 && iy[NK - 1] == 1 && !no_fold;
     for (int i = 0; i < NK; ++i) unit = unit && ix[i] == ix[NK - 1 - i];
     if constexpr (!CLAMP) {
         if (unit) {
-            hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, true>), dim3((unsigned)items), dim3(64), 0, s, a, kx, ky);
+            hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, true>), grid, dim3(64), 0, s, a, kx, ky);
             return launch_ok();
         }
     }
-    hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, false>), dim3((unsigned)items), dim3(64), 0, s, a, kx, ky);
+    hipLaunchKernelGGL((k_sep_stream<SP, NK, CLAMP, DOWN2, 1, false>), grid, dim3(64), 0, s, a, kx, ky);
     return launch_ok();
 }
 
@@ -457,16 +415,14 @@ int try_sep_stream(const FrameBatch &b, const int32_t *ix, const int32_t *iy, in
     if (src.pixel != ZG_PIXEL_U8 && src.pixel != ZG_PIXEL_RGB_U8 && src.pixel != ZG_PIXEL_RGBA_U8) return -1;
     const bool down2 = src.rows == 2 * dst.rows && src.cols == 2 * dst.cols; // blur then 2:1 bilinear
     if (!down2 && (src.rows != dst.rows || src.cols != dst.cols)) return -1;
-    const size_t sp = pixel_size(src.pixel), src_pitch = src.stride * sp, dst_pitch = dst.stride * sp; // bytes per pixel, bytes between rows
+    const size_t sp = pixel_size(src.pixel), dst_pitch = dst.stride * sp; // bytes per pixel, bytes between rows
     // a single grey plane is the one case the LDS-tiled kernel still wins (10.4 against 11.9 us at 4096^2): 16 pixels per lane leave
     // it little halo to re-convolve, and a 4 KiB-wide row gives this kernel only four strips across
     if (sp == 1 && b.n == 1) return -1;
     if (nk != 3 && nk != 5 && nk != 7 && nk != 9) return -1;
     if ((nk / 2 + 1) * sp > 16) return -1;
+    if (!strip_shape_ok(b, sp, dst_pitch)) return -1;
     const uint64_t rb = (uint64_t)src.cols * sp;
-    if (rb % 16 || src_pitch % 16 || b.src_frame % 16 || ((uintptr_t)src.data & 15)) return -1;
-    if (rb % 1024 == 16) return -1; // the last strip would be one lane wide: that lane is first and last at once
-    if (src.cols < 64 || src.rows < 16 || rb > 0x3fffffffu || src_pitch > 0x7fffffffu || dst_pitch > 0x7fffffffu) return -1;
     if (down2) {
         if (sp != 4 || src.rows % 2 || rb % 32 || dst_pitch % 8 || b.dst_frame % 8 || ((uintptr_t)dst.data & 7)) return -1;
     } else {

@@ -1,5 +1,5 @@
 // sobel_stream.hip — Image(u8).sobel and Image(Rgba(u8)).sobel as a register-resident stream: one WAVE walks a 1024-byte-wide column
-// strip from top to bottom (the skeleton of conv_sep_stream.hip / conv2d_stream.hip), no LDS, no barrier.
+// strip from top to bottom (the strip walker of zg_stream.h), no LDS, no barrier.
 //
 // Contract (reference src/image/edges.zig:33-70): grey = as(f32, convertColor(u8, px)); gx, gy = the 3 x 3 Sobel sums of the grey plane
 // with .replicate borders, in f32; out = @trunc(@max(0, @min(255, @sqrt(gx * gx + gy * gy) / 4))).
@@ -30,18 +30,6 @@
 
 namespace zg {
 
-struct SobelStreamArgs {
-    const uint8_t *src;
-    uint8_t *dst;
-    uint64_t src_pitch, dst_pitch; // bytes between rows
-    uint64_t src_frame, dst_frame; // bytes between frames (blockIdx.y)
-    int32_t rows, row_bytes;       // source rows, bytes per source row
-    int32_t strips_x, strips_y;
-    int32_t strip_rows;
-    uint32_t src_span, dst_span;
-    int32_t fast_ok;
-};
-
 template <int B> __device__ __forceinline__ float ubyte_f32(uint32_t dword) { return (float)((dword >> (8 * B)) & 0xffu); } // v_cvt_f32_ubyteB
 __device__ __forceinline__ float dpp_below(float old, float v) { return __builtin_bit_cast(float, from_lane_below(__builtin_bit_cast(uint32_t, old), __builtin_bit_cast(uint32_t, v))); }
 __device__ __forceinline__ float dpp_above(float old, float v) { return __builtin_bit_cast(float, from_lane_above(__builtin_bit_cast(uint32_t, old), __builtin_bit_cast(uint32_t, v))); }
@@ -60,7 +48,7 @@ __device__ __forceinline__ uint32_t sobel_byte(float m, uint32_t b, uint32_t old
 }
 
 template <int SP, int DM>
-__global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
+__global__ __launch_bounds__(64) void k_sobel_stream(StripArgs a) {
     static_assert(SP == 1 || SP == 4, "grey or Rgba(u8) sources");
     constexpr int NPX = 16 / SP;  // pixels a lane owns per row
     constexpr int HB = 1;         // one halo dword per side: one Rgba pixel, or the grey pixel in its byte 3 / byte 0
@@ -68,61 +56,20 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
     constexpr int NG = NPX + 2;   // grey columns a lane holds per row: x - 1 .. x + NPX
 
     const uint32_t w = xcd_major((uint32_t)blockIdx.x, (uint32_t)gridDim.x);
-    const int sy = (int)(w / (uint32_t)a.strips_x), sx = (int)(w - (uint32_t)sy * (uint32_t)a.strips_x);
     const uint8_t *srcf = a.src + (size_t)blockIdx.y * a.src_frame;
     uint8_t *dstf = a.dst + (size_t)blockIdx.y * a.dst_frame;
-
-    const int lx = (int)threadIdx.x;
-    const int rb = a.row_bytes, x0 = sx * 1024;
-    const int voff = x0 + 16 * lx;
-    const int dvoff = voff / SP; // one output byte per source pixel
-    const int last_lane = (min(rb - x0, 1024) >> 4) - 1;
-    const bool left_edge = sx == 0, right_edge = x0 + 1024 >= rb;
-    // lane 0: the dword before the strip, every other lane: the dword after it (the last lane's); clamped into the row at the image's ends,
-    // where .replicate takes the lane's own outer pixel instead
-    const int off_h = lx == 0 ? (left_edge ? 0 : x0 - 4) : (right_edge ? rb - 4 : x0 + 1024);
-    const int y0 = sy * a.strip_rows;
+    // the halo dword: lane 0 the one before the strip, every other lane the one after it (the last lane's); clamped into the row at the
+    // image's ends, where .replicate takes the lane's own outer pixel instead
+    const StripLane<HB> L(a, w, false);
+    const int lx = L.lx, last_lane = L.last_lane, y0 = L.y0;
     const int out_rows = min(y0 + a.strip_rows, a.rows) - y0;
     const int n_in = (out_rows + 2 + D - 1) / D * D;
-
-    const uint32_t dst_rb = (uint32_t)rb / SP;
-    const auto src_all = __builtin_amdgcn_make_buffer_rsrc((void *)srcf, (short)0, (int)a.src_span, 0x00020000);
-    const auto dst_all = __builtin_amdgcn_make_buffer_rsrc((void *)dstf, (short)0, (int)a.dst_span, 0x00020000);
     const bool fast = a.fast_ok && y0 - 1 >= 0 && y0 - 1 + n_in + D <= a.rows;
-    const bool full = last_lane == 63;
 
-    auto run = [&](auto fast_tag, auto edge_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
+    strip_dispatch(fast, L.edges, [&](auto fast_tag, auto edge_tag) {
         constexpr bool EDGE = decltype(edge_tag)::value;
-        uint32_t s_next = (uint32_t)(y0 - 1) * (uint32_t)a.src_pitch;
-        uint32_t d_next = (uint32_t)y0 * (uint32_t)a.dst_pitch;
-        auto load_row = [&](int y) -> RowIn<HB> {
-            RowIn<HB> r;
-            if constexpr (FAST) {
-                r.v = __builtin_amdgcn_raw_buffer_load_b128(src_all, voff, (int)s_next, 0);
-                HaloLoad<HB>::run(src_all, off_h, (int)s_next, r.h);
-                s_next += (uint32_t)a.src_pitch;
-            } else {
-                const int gr = min(max(y, 0), a.rows - 1); // .replicate
-                const uint8_t *row = srcf + (size_t)(uint32_t)gr * a.src_pitch;
-                const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)row, (short)0, rb, 0x00020000);
-                r.v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0);
-                HaloLoad<HB>::run(rsrc, off_h, 0, r.h);
-            }
-            return r;
-        };
-        auto store_row = [&](auto o, int gy) {
-            if constexpr (FAST) {
-                if (full) st_unit(o, dst_all, dvoff + (int)d_next);
-                else if (lx <= last_lane) st_unit(o, dst_all, dvoff + (int)d_next);
-                d_next += (uint32_t)a.dst_pitch;
-            } else {
-                const uint32_t row_ok = (uint32_t)gy < (uint32_t)a.rows ? ~0u : 0u;
-                uint8_t *row = dstf + (size_t)((uint32_t)gy & row_ok) * a.dst_pitch;
-                const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)row, (short)0, (int)(dst_rb & row_ok), 0x00020000);
-                st_unit(o, rsrc, dvoff); // a lane's unit is all inside the row or all outside it
-            }
-        };
+        // .replicate rows; one output byte per source pixel: a lane's unit is 16 / SP bytes
+        StripRows<HB, 1, decltype(fast_tag)::value, SP == 4 ? 2 : 0, 0, true> rows(a, L, srcf, dstf, ZG_BORDER_REPLICATE);
         // grey columns x - 1 .. x + NPX of one source row
         auto grey_row = [&](const RowIn<HB> &r, float (&g)[NG]) {
             float gh; // the strip's outer column this lane can supply: lane 0 its left one, the others the right one
@@ -140,15 +87,15 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
             g[0] = dpp_below(gh, g[NPX]);
             g[NG - 1] = dpp_above(gh, g[1]);
             if constexpr (EDGE) { // .replicate at the row's ends; a row that ends inside the strip
-                if (left_edge) g[0] = lx == 0 ? g[1] : g[0];
-                if (right_edge) g[NG - 1] = lx == last_lane ? g[NPX] : g[NG - 1];
+                if (L.left_edge) g[0] = lx == 0 ? g[1] : g[0];
+                if (L.right_edge) g[NG - 1] = lx == last_lane ? g[NPX] : g[NG - 1];
             }
         };
 
         RowIn<HB> ahead[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            ahead[i] = load_row(y0 - 1 + i);
+            ahead[i] = rows.load(y0 - 1 + i);
             __builtin_amdgcn_sched_barrier(0);
         }
         float G[3][NG]; // grey rows, source row q of the strip (row y0 - 1 + q of the image) in slot q % 3
@@ -161,7 +108,7 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
             for (int u = 0; u < D; ++u) {
                 const int q = qb + u;
                 grey_row(ahead[u], G[u % 3]);
-                ahead[u] = load_row(y0 - 1 + q + D);
+                ahead[u] = rows.load(y0 - 1 + q + D);
                 if (q < 2) continue; // wave-uniform
                 const float(&top)[NG] = G[(u + 1) % 3], (&mid)[NG] = G[(u + 2) % 3], (&bot)[NG] = G[u % 3]; // rows q - 2, q - 1, q
                 float sm[NG], df[NG];
@@ -183,42 +130,21 @@ __global__ __launch_bounds__(64) void k_sobel_stream(SobelStreamArgs a) {
                     }
                     o[d] = pk;
                 }
-                if constexpr (SP == 4) store_row(o[0], y0 + q - 2);
-                else store_row(u32x4{o[0], o[1], o[2], o[3]}, y0 + q - 2);
+                if constexpr (SP == 4) rows.store(o[0], y0 + q - 2);
+                else rows.store(u32x4{o[0], o[1], o[2], o[3]}, y0 + q - 2);
             }
         }
-    };
-    const bool edges = left_edge || right_edge || last_lane != 63;
-    if (fast && !edges) run(std::true_type{}, std::false_type{});
-    else if (fast) run(std::true_type{}, std::true_type{});
-    else run(std::false_type{}, std::true_type{});
+    });
 }
 
 template <int SP>
 static int launch_sobel_stream(const FrameBatch &b, hipStream_t s) {
-    const zg_image *src = b.src, *dst = b.dst;
-    const uint32_t n = b.n;
-    SobelStreamArgs a;
-    a.src = (const uint8_t *)src->data;
-    a.dst = (uint8_t *)dst->data;
-    a.src_pitch = src->stride * (size_t)SP;
-    a.dst_pitch = dst->stride;
-    a.src_frame = b.src_frame;
-    a.dst_frame = b.dst_frame;
-    a.rows = (int32_t)src->rows;
-    a.row_bytes = (int32_t)(src->cols * (uint32_t)SP);
-    a.strips_x = (int32_t)ceil_div((unsigned)a.row_bytes, 1024u);
-    int r = (int)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)src->rows * a.strips_x * n + 4095) / 4096, 16), 64);
+    StripArgs a{};
+    dim3 grid;
+    int r = (int)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)b.src->rows * strips_across(b.src, SP) * b.n + 4095) / 4096, 16), 64);
     while ((r + 2) % 3) ++r; // (strip rows + 2) % D == 0
-    a.strip_rows = r;
-    a.strips_y = (int32_t)ceil_div(src->rows, (unsigned)a.strip_rows);
-    const uint64_t sspan = (uint64_t)(src->rows - 1) * a.src_pitch + (uint64_t)a.row_bytes, dspan = (uint64_t)(src->rows - 1) * a.dst_pitch + src->cols;
-    a.fast_ok = sspan <= 0xffffffffu && dspan <= 0xffffffffu;
-    a.src_span = (uint32_t)sspan;
-    a.dst_span = (uint32_t)dspan;
-    const uint64_t items = (uint64_t)a.strips_x * a.strips_y;
-    if (items > 0x7fffffffu || n > MAX_FRAMES_PER_LAUNCH) return -1;
-    hipLaunchKernelGGL((k_sobel_stream<SP, 1>), dim3((unsigned)items, n), dim3(64), 0, s, a);
+    if (strip_args(a, grid, b, ZG_BORDER_REPLICATE, SP, 1, false, r, 0xffffffffu, true) != 0) return -1;
+    hipLaunchKernelGGL((k_sobel_stream<SP, 1>), grid, dim3(64), 0, s, a);
     return launch_ok();
 }
 
@@ -227,12 +153,9 @@ int try_sobel_stream(const FrameBatch &b, hipStream_t s) {
     const zg_image *src = b.src, *dst = b.dst;
     if (src->pixel != ZG_PIXEL_U8 && src->pixel != ZG_PIXEL_RGBA_U8) return -1;
     const int sp = src->pixel == ZG_PIXEL_U8 ? 1 : 4;
-    const uint64_t rb = (uint64_t)src->cols * (uint64_t)sp, sp_pitch = (uint64_t)src->stride * sp;
     const unsigned dalign = sp == 1 ? 16 : 4; // the lane's output unit
-    if (rb % 16 || sp_pitch % 16 || b.src_frame % 16 || ((uintptr_t)src->data & 15)) return -1;
+    if (!strip_shape_ok(b, sp, dst->stride)) return -1;
     if (dst->stride % dalign || b.dst_frame % dalign || ((uintptr_t)dst->data & (dalign - 1))) return -1;
-    if (rb % 1024 == 16) return -1; // the last strip would be one lane wide
-    if (src->cols < 64 || src->rows < 16 || rb > 0x3fffffffu || sp_pitch > 0x7fffffffu || dst->stride > 0x7fffffffu) return -1;
     return sp == 1 ? launch_sobel_stream<1>(b, s) : launch_sobel_stream<4>(b, s);
 }
 

@@ -67,6 +67,7 @@ bool taps_pack_u16(const int32_t *ix, int nkx, const int32_t *iy, int nky, TapSu
 
 // u8 separable convolution of a batch of frames, one wave per column strip (conv_sep_stream.hip), and the tiled Rgba(u8) form of the
 // same (conv_sep_rgba8.hip). A destination of exactly half the source's rows and columns asks for blur then 2:1 bilinear (Rgba(u8) only).
+// The u8 strip routes (this one, conv2d_stream.hip, sobel_stream.hip) share their arguments, filler and shape test: zg_stream.h.
 int try_sep_stream(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
 int try_sep_rgba8_batch(const FrameBatch &b, const int32_t *ix, const int32_t *iy, int nk, int border, hipStream_t s);
 
