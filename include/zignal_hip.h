@@ -767,4 +767,9 @@ ZG_API void zg_jpeg_free(void *p);
  * Canvas line commands: a module of its own in the same way (_QR_SIGNATURES, zig/zignal_hip_qr.zig). */
 #include "zignal_hip_qr.h"
 
+/* SimilarityTransform.find, AffineTransform.find and ProjectiveTransform.find (src/geometry/transforms.zig) from point arrays or a match
+ * list, and Image.warp with the fitted matrix read from device memory: a module of its own in the same way (_TRANSFORM_SIGNATURES,
+ * zig/zignal_hip_transform.zig). */
+#include "zignal_hip_transform.h"
+
 #endif /* ZIGNAL_HIP_H */

@@ -202,6 +202,17 @@ FDM_ROUTE_COLOR, FDM_ROUTE_SCALAR, FDM_ROUTE_GRAY_TARGET = range(3)
 FDM_STATUS_TYPE_MISMATCH = -1
 
 
+class ZgTransformFit(C.Structure):
+    """zg_transform_fit: the result of a fit (include/zignal_hip_transform.h). 128 bytes."""
+    _fields_ = [("kind", C.c_int32), ("status", C.c_int32), ("n_points", C.c_uint32), ("svd_converged", C.c_uint32), ("m64", C.c_double * 9),
+                ("m32", C.c_float * 9), ("reserved", C.c_uint32)]
+
+
+SCALAR_F32, SCALAR_F64 = range(2)
+FIT_OK, FIT_NOT_CONVERGED, FIT_RANK_DEFICIENT, FIT_BAD_COUNT, FIT_BAD_INPUT = range(5)
+FIT_MAX_POINTS, FIT_MAX_POINTS_AFFINE = 65536, 4096  # ZG_FIT_MAX_*
+
+
 class ZignalError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"zignal_hip status {status}: {message}")
@@ -601,6 +612,25 @@ _QR_SIGNATURES = {
 _QR_RESTYPES = {"zg_qr_sizeof_detection": C.c_size_t, "zg_qr_sizeof_grid": C.c_size_t, "zg_qr_scratch_bytes": C.c_size_t}
 QR_EXPORTED_SYMBOLS = tuple(_QR_SIGNATURES)
 
+# the geometry-fitting module: every symbol include/zignal_hip_transform.h declares
+_FIT = C.POINTER(ZgTransformFit)
+_TRANSFORM_SIGNATURES = {
+    "zg_transform_sizeof_fit": [],
+    "zg_transform_chunk": [],
+    "zg_transform_fit_points": [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "zg_transform_fit_matches": [C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_void_p],
+    "zg_transform_fit_points_host": [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, _U32P, _FIT],
+    "zg_transform_fit_matches_host": [C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _U32P, C.c_int, _FIT],
+    "zg_transform_project_points": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "zg_transform_project_points_host": [_FIT, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32],
+    "zg_transform_invert": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "zg_transform_invert_host": [_FIT, C.c_int, _FIT],
+    "zg_warp_fitted": [_IMG, _IMG, C.c_void_p, _METHOD, C.c_void_p],
+}
+_TRANSFORM_RESTYPES = {"zg_transform_sizeof_fit": C.c_size_t, "zg_transform_chunk": C.c_uint32}
+TRANSFORM_EXPORTED_SYMBOLS = tuple(_TRANSFORM_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -614,7 +644,8 @@ def lib() -> C.CDLL:
                                 (_HOUGH_SIGNATURES, _HOUGH_RESTYPES), (_FLOOD_SIGNATURES, _FLOOD_RESTYPES), (_METRICS_SIGNATURES, _METRICS_RESTYPES),
                                 (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
                                 (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES),
-                                (_TRACER_SIGNATURES, _TRACER_RESTYPES), (_QR_SIGNATURES, _QR_RESTYPES)):
+                                (_TRACER_SIGNATURES, _TRACER_RESTYPES), (_QR_SIGNATURES, _QR_RESTYPES),
+                                (_TRANSFORM_SIGNATURES, _TRANSFORM_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes
@@ -632,6 +663,8 @@ def lib() -> C.CDLL:
         for name, struct in (("zg_qr_sizeof_detection", ZgQrDetection), ("zg_qr_sizeof_grid", ZgQrGrid)):
             if getattr(l, name)() != C.sizeof(struct):
                 raise ImportError(f"{LIB_PATH}: {name}() is {getattr(l, name)()} in the library, {C.sizeof(struct)} in this binding: rebuild the library")
+        if l.zg_transform_sizeof_fit() != C.sizeof(ZgTransformFit):
+            raise ImportError(f"{LIB_PATH}: zg_transform_sizeof_fit() is {l.zg_transform_sizeof_fit()} in the library, {C.sizeof(ZgTransformFit)} in this binding: rebuild the library")
         _lib = l
     return _lib
 

@@ -533,6 +533,62 @@ int warp_frames(const FrameBatch &fb, int kind, const float *mat, const zg_metho
     return launch_geom(fb, g, method, ZG_BORDER_MIRROR, s);
 }
 
+// ---- Image.warp with the matrix of a device record (include/zignal_hip_transform.h) -----------------------------------------
+// k_geom's tile and its sampler, with the kind and the nine f32 coefficients read from a zg_transform_fit in device memory instead of the
+// kernel arguments: a kernel of its own, so that the k_geom instantiations stay the code they were (profiles/transform_fit_isa.txt). A
+// record whose status is not ZG_FIT_OK ends every workgroup before it writes. The record's address is the same for every lane, so the
+// loads are scalar; no wave staging (the plain gather serves every pixel type and kernel).
+template <int PIX, int KIND>
+__global__ __launch_bounds__(256) void k_geom_fitted(DImg src, DImg dst, const zg_transform_fit *fit, MethodArg m, int tiles_x) {
+    using P = Px<PIX>;
+    using Vec = typename P::Vec;
+    if (fit->status != ZG_FIT_OK) return;
+    GeomParams g;
+    g.mode = fit->kind == ZG_TRANSFORM_PROJECTIVE ? GEOM_PROJECTIVE : GEOM_AFFINE;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) g.p[i] = fit->m32[i];
+    g.stage = 0;
+    const int wg = xcd_major((int)blockIdx.x, (int)gridDim.x);
+    const int ty = wg / tiles_x, tx = wg - ty * tiles_x;
+    const int c = tx * 64 + (int)(threadIdx.x & 63);
+    const int r = ty * 4 + (int)(threadIdx.x >> 6);
+    if (c >= dst.cols || r >= dst.rows) return;
+    float sx, sy;
+    source_coord(g, c, r, sx, sy);
+    Vec v;
+    if (!interpolate<PIX, KIND, false>(src, sx, sy, m, ZG_BORDER_MIRROR, v, (Vec *)nullptr)) v = P::zero();
+    P::store(dst.data, (size_t)r * dst.stride + (size_t)c, v);
+}
+
+template <int PIX, int KIND> static int launch_geom_fitted_k(const zg_image *src, const zg_image *dst, const zg_transform_fit *fit, const MethodArg &m, hipStream_t s) {
+    const int tiles_x = (int)ceil_div(dst->cols, 64), tiles_y = (int)ceil_div(dst->rows, 4);
+    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;
+    ZG_REQUIRE(tiles <= 0x7fffffffu, ZG_ERR_INVALID_ARGUMENT, "too many tiles in one launch (%llu)", (unsigned long long)tiles);
+    hipLaunchKernelGGL((k_geom_fitted<PIX, KIND>), dim3((unsigned)tiles), dim3(256), 0, s, dimg(src), dimg(dst), fit, m, tiles_x);
+    return launch_ok("k_geom_fitted");
+}
+
+int warp_fitted(const zg_image *src, const zg_image *dst, const zg_transform_fit *fit, const zg_method *method, hipStream_t s) {
+    int rc;
+    if ((rc = check_pair(src, dst, "warp_fitted")) || (rc = check_method(method))) return rc;
+    ZG_REQUIRE(fit != nullptr, ZG_ERR_INVALID_ARGUMENT, "warp_fitted: null record");
+    if (dst->rows == 0 || dst->cols == 0) return ZG_OK;
+    LutHolder lut(s);
+    if ((rc = device_lanczos_lut(method, s, lut))) return rc;
+    const MethodArg m{method->kind, method->b, method->c, lut.dev};
+    return dispatch_pixel(src->pixel, [&](auto tag) -> int {
+        constexpr int PIX = decltype(tag)::value;
+        switch (method->kind) {
+        case ZG_INTERP_NEAREST: return launch_geom_fitted_k<PIX, ZG_INTERP_NEAREST>(src, dst, fit, m, s);
+        case ZG_INTERP_BILINEAR: return launch_geom_fitted_k<PIX, ZG_INTERP_BILINEAR>(src, dst, fit, m, s);
+        case ZG_INTERP_BICUBIC: return launch_geom_fitted_k<PIX, ZG_INTERP_BICUBIC>(src, dst, fit, m, s);
+        case ZG_INTERP_CATMULL_ROM: return launch_geom_fitted_k<PIX, ZG_INTERP_CATMULL_ROM>(src, dst, fit, m, s);
+        case ZG_INTERP_MITCHELL: return launch_geom_fitted_k<PIX, ZG_INTERP_MITCHELL>(src, dst, fit, m, s);
+        default: return launch_geom_fitted_k<PIX, ZG_INTERP_LANCZOS>(src, dst, fit, m, s);
+        }
+    });
+}
+
 // ---- rotate (transforms.zig:112-212, :385-462) -----------------------------------------------------
 static float mod_tau(float a) { // @mod(angle, tau): floored
     const float tau = 6.28318530717958647692f;
@@ -834,6 +890,9 @@ int zg_warp(const zg_image *src, const zg_image *dst, int kind, const float *m, 
 }
 int zg_warp_host(const zg_image *src, const zg_image *dst, int kind, const float *m, const zg_method *method) {
     return host_src_dst(src, dst, [&](const zg_image *a, const zg_image *b) { return warp_frames(FrameBatch{a, b}, kind, m, method, nullptr); });
+}
+int zg_warp_fitted(const zg_image *src, const zg_image *dst, const zg_transform_fit *fit_dev, const zg_method *method, zg_stream stream) {
+    return warp_fitted(src, dst, fit_dev, method, as_stream(stream));
 }
 
 int zg_rotate_into(const zg_image *src, const zg_image *dst, float angle, float cos_a, float sin_a,
