@@ -772,4 +772,8 @@ ZG_API void zg_jpeg_free(void *p);
  * zig/zignal_hip_transform.zig). */
 #include "zignal_hip_transform.h"
 
+/* Seam carving (examples/src/seam_carving.zig): the energy map, the seam, its removal and the iteration over Image.sobel: a module of its
+ * own in the same way (_SEAM_SIGNATURES, zig/zignal_hip_seam.zig). */
+#include "zignal_hip_seam.h"
+
 #endif /* ZIGNAL_HIP_H */

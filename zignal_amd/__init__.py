@@ -20,8 +20,9 @@ from .fdm import FeatureDistributionMatching, NoSourceSet, NoTargetSet
 from .tracer import Tracer
 from .qr import QrDetector, QrGrid
 from .transform import FIT_DTYPE, FitError, FittedTransform
+from .seam import seam_band_rows, seam_energy, seam_find, seam_strip_cols
 
-__all__ = ["FIT_DTYPE", "FitError", "FittedTransform", "transform", "QrDetector", "QrGrid", "Tracer", "FeatureDistributionMatching", "NoTargetSet", "NoSourceSet", "Canvas", "DRAW_CMD_DTYPE", "canvas_tile", "BitmapFont", "GLYPH_DTYPE", "TEXT_CMD_DTYPE", "Image", "ImagePyramid", "Fast", "Orb", "BruteForceMatcher", "MatchStats", "MATCH_DTYPE", "HoughTransform", "HoughLine", "HOUGH_LINE_DTYPE", "FloodFillOptions", "flood_fill_bound", "flood_fill_tile", "METRIC_RESULT_DTYPE", "psnr_from_mse", "ssim_window", "sum_f64_chunk", "sum_f64_sequential", "DitherMode", "PaletteMode", "build_palette", "dither_geometry", "median_cut_from_histogram", "palette_lut", "KEYPOINT_DTYPE", "BINARY_DESCRIPTOR_DTYPE", "BinaryDescriptor", "Interpolation", "BorderMode", "Blending", "ProjectiveTransform", "AffineTransform",
+__all__ = ["seam_band_rows", "seam_strip_cols", "seam_energy", "seam_find","FIT_DTYPE", "FitError", "FittedTransform", "transform", "QrDetector", "QrGrid", "Tracer", "FeatureDistributionMatching", "NoTargetSet", "NoSourceSet", "Canvas", "DRAW_CMD_DTYPE", "canvas_tile", "BitmapFont", "GLYPH_DTYPE", "TEXT_CMD_DTYPE", "Image", "ImagePyramid", "Fast", "Orb", "BruteForceMatcher", "MatchStats", "MATCH_DTYPE", "HoughTransform", "HoughLine", "HOUGH_LINE_DTYPE", "FloodFillOptions", "flood_fill_bound", "flood_fill_tile", "METRIC_RESULT_DTYPE", "psnr_from_mse", "ssim_window", "sum_f64_chunk", "sum_f64_sequential", "DitherMode", "PaletteMode", "build_palette", "dither_geometry", "median_cut_from_histogram", "palette_lut", "KEYPOINT_DTYPE", "BINARY_DESCRIPTOR_DTYPE", "BinaryDescriptor", "Interpolation", "BorderMode", "Blending", "ProjectiveTransform", "AffineTransform",
            "SimilarityTransform", "Pipeline", "Step", "Multi", "gaussian_kernel", "gaussian_blur_planes", "convolve_separable_planes", "lanczos_plane_weights", "DimensionMismatch", "InvalidArgument", "CodecError", "ZignalError", "lib", "png", "jpeg"]
 
 from . import fdm, jpeg, png, transform  # noqa: E402,F401

@@ -631,6 +631,23 @@ _TRANSFORM_SIGNATURES = {
 _TRANSFORM_RESTYPES = {"zg_transform_sizeof_fit": C.c_size_t, "zg_transform_chunk": C.c_uint32}
 TRANSFORM_EXPORTED_SYMBOLS = tuple(_TRANSFORM_SIGNATURES)
 
+# the seam-carving module: every symbol include/zignal_hip_seam.h declares
+_SEAM_SIGNATURES = {
+    "zg_seam_band_rows": [],
+    "zg_seam_strip_cols": [],
+    "zg_seam_energy": [_IMG, C.c_void_p, C.c_void_p],
+    "zg_seam_find": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "zg_seam_remove": [_IMG, C.c_void_p, _IMG, C.c_void_p],
+    "zg_seam_carve": [_IMG, _IMG, C.c_uint32, C.c_int, _IMG, C.c_void_p, C.c_void_p],
+    "zg_seam_energy_host": [_IMG, C.c_void_p],
+    "zg_seam_find_host": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "zg_seam_remove_host": [_IMG, C.c_void_p, _IMG],
+    "zg_seam_carve_host": [_IMG, _IMG, C.c_uint32, C.c_int, _IMG, C.c_void_p],
+}
+_SEAM_RESTYPES = {"zg_seam_band_rows": C.c_uint32, "zg_seam_strip_cols": C.c_uint32}
+SEAM_EXPORTED_SYMBOLS = tuple(_SEAM_SIGNATURES)
+SEAM_VERTICAL, SEAM_HORIZONTAL = range(2)  # ZG_SEAM_VERTICAL, ZG_SEAM_HORIZONTAL
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -645,7 +662,7 @@ def lib() -> C.CDLL:
                                 (_QUANTIZE_SIGNATURES, _QUANTIZE_RESTYPES), (_CANVAS_SIGNATURES, _CANVAS_RESTYPES),
                                 (_TEXT_SIGNATURES, _TEXT_RESTYPES), (_FDM_SIGNATURES, _FDM_RESTYPES),
                                 (_TRACER_SIGNATURES, _TRACER_RESTYPES), (_QR_SIGNATURES, _QR_RESTYPES),
-                                (_TRANSFORM_SIGNATURES, _TRANSFORM_RESTYPES)):
+                                (_TRANSFORM_SIGNATURES, _TRANSFORM_RESTYPES), (_SEAM_SIGNATURES, _SEAM_RESTYPES)):
             for name, argtypes in table.items():
                 fn = getattr(l, name)  # AttributeError if the library does not export it
                 fn.argtypes = argtypes

@@ -330,6 +330,16 @@ template <template <typename> class Img, typename T> class Ops {
         else check(zg_flood_fill_host(&s, row, col, (const void *)&fill_value, &o, &filled));
         return filled;
     }
+    // examples/src/seam_carving.zig:104-144, n times: sobel, computeEnergy, computeSeam, removeSeam. The result is a new rows x (cols - n)
+    // image (horizontal: (rows - n) x cols, the library's own definition through the transposed frame); this image is left unchanged.
+    // seams, when not null, receives n * rows words (n * cols for horizontal): host memory for an Image, device memory for a DeviceImage,
+    // whose carve is enqueued on stream().
+    Derived seamCarve(uint32_t n, bool horizontal = false, uint32_t *seams = nullptr) const {
+        Derived out = horizontal ? Derived::like(self(), rows > n ? rows - n : 0, cols) : Derived::like(self(), rows, cols > n ? cols - n : 0);
+        const zg_image s = desc(), d = out.desc();
+        run(zg_seam_carve, zg_seam_carve_host, &s, &d, n, horizontal ? ZG_SEAM_HORIZONTAL : ZG_SEAM_VERTICAL, (const zg_image *)nullptr, seams);
+        return out;
+    }
     // ---- quantisation and dithering (quantize.zig, dither.zig, gif.zig:875-920): DeviceImage only, enqueued on stream() ----
     // counts_device and first_device are 32768 device words each (quantize.zig:188-237; first: the raster index of a cell's first pixel)
     void colorHistogram(uint32_t *counts_device, uint32_t *first_device) const {

@@ -290,6 +290,18 @@ class Image:
                                           C.c_void_p(count.data_ptr()) if count is not None else None, self._stream()))
         return self
 
+    # ---- seam carving (reference examples/src/seam_carving.zig; zignal_amd/seam.py) -------------------------------------------
+    def seam_carve(self, n: int, axis="vertical", out=None, seams=None) -> "Image":
+        """n iterations of the reference's seam_carve (sobel, computeEnergy, computeSeam, removeSeam): content-aware resize to
+        rows x (cols - n), or (rows - n) x cols for axis "horizontal". This image is left unchanged. See zignal_amd.seam.seam_carve."""
+        from . import seam
+        return seam.seam_carve(self, n, axis, out, seams)
+
+    def seam_remove(self, seam, out=None) -> "Image":
+        """removeSeam, out of place: row r loses column seam[r]. See zignal_amd.seam.seam_remove."""
+        from . import seam as S
+        return S.seam_remove(self, seam, out)
+
     # ---- metrics (reference src/image/metrics.zig) -------------------------------------------------------------------------
     def _metric(self, name: str, other: "Image", result, window=None, ssim_map=None):
         from . import metrics as M
